@@ -15,9 +15,16 @@ dealt round robin).  Strong scaling: the frame is fixed, the work is split
 over the ranks.  The JSON's `c4` object times the north star's own scene
 (C4) on the same ranks.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--c4-steps K]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
     python -m torch.distributed.run --nproc-per-node 1 ... bench.py --force-dist   (the RCCL path at one rank)
+
+A plain run sets up, warms up, times the K steps and prints the line; its `c4`, `cpu_baseline` and
+`postprocess` are null.  Those three take runs of their own (C4 frames, the oracle on the host's cores,
+k_post calls) and are measured only with --full.  --dump-outputs DIR saves what the last timed step
+computed (the accumulated frame and the step's counts) as DIR/<name>.npy, so that two builds can be
+compared output for output: the scene, the camera and the sample keys depend on the arguments alone.
 
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel: the stage
 with the most GPU time in the timed region (k_shade on C3), algorithmic bytes =
@@ -30,7 +37,7 @@ flight, `isolated` the serialized figures from the rocprofv3 --pmc runs, and
 sample over wall time), and `traversal` the trace kernels' step fetches (128 B per
 step, the timed frames' own rt_stats::trace_steps) over their launch time.  The
 frame's TraversalStats (rt_stats::traversal, the reference's per-frame counters)
-are in `traversal_stats`.  `cpu_baseline` is the CPU restatement (oracle/,
+are in `traversal_stats`.  `cpu_baseline` (--full) is the CPU restatement (oracle/,
 reference-stream RNG, 64x64 tile queue) timed on this box's cores over a
 bounded sample of the same workload.
 """
@@ -202,6 +209,30 @@ def pmc_figures(tj, kname, units_per_frame, alg, launches_per_frame):
             "traffic_per_frame": round(hbm), "traffic_ratio": round(hbm / alg, 3)}
 
 
+DUMP_BYTES = 60 * 10**6        # --dump-outputs: the arrays of one run, in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(dirname, frame, counts):
+    """--dump-outputs: the last timed step's accumulated frame (float32 (h, w, 4)) as frame.npy and
+    its counts (samples, closest-hit rays, shadow rays, traced closest-hit / shadow rays) as
+    counts.npy (float64).  A frame over the size limit (C5's 4K) is saved as a fixed, seeded sample
+    of its pixels instead: frame_sample.npy (float32 (k, 4)) and the pixels' flat indices y*w + x,
+    ascending, in frame_sample_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    counts = np.asarray(counts, np.float64)
+    np.save(os.path.join(dirname, "counts.npy"), counts)
+    px = np.ascontiguousarray(frame, np.float32).reshape(-1, 4)
+    room = DUMP_BYTES - counts.nbytes
+    if px.nbytes <= room:
+        np.save(os.path.join(dirname, "frame.npy"), px.reshape(frame.shape))
+        return
+    k = room // (px.itemsize * 4 + 8)               # a pixel and its index
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], k, replace=False))
+    np.save(os.path.join(dirname, "frame_sample.npy"), px[idx])
+    np.save(os.path.join(dirname, "frame_sample_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -212,7 +243,14 @@ def main():
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--pool", type=int, default=0, help="in-flight path pool size (0 = default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the C4 frames (--c4-steps), the CPU baseline "
+                         "(unless --no-cpu-baseline) and the output pass; a plain run reports them as null")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 saves what the last timed step computed as DIR/<name>.npy: the accumulated "
+                         "frame (frame.npy, float32; a seeded pixel sample of a frame over 60 MB) and the step's "
+                         "counts (counts.npy, float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--shard-index", type=int, default=0, help="with --shard-of: which rank's share (diagnostic)")
     ap.add_argument("--shard-mode", choices=["tiles", "passes"], default="passes",
                     help="what a rank's share of the frame is: a range of sample passes over every tile (default: "
@@ -228,7 +266,7 @@ def main():
                     help="nccl (= RCCL over xGMI, the product path) or gloo (framebuffer reduced through host "
                          "memory: lets several ranks share one GPU in the tests)")
     ap.add_argument("--c4-steps", type=int, default=5,
-                    help="also time the north star's own scene (C4, 1080p 256 spp) for this many frames "
+                    help="with --full: also time the north star's own scene (C4, 1080p 256 spp) for this many frames "
                          "after one warm-up frame, same ranks and sharding (0 = skip)")
     ap.add_argument("--dump-frame", default="",
                     help="rank 0 saves the accumulated frame of the last timed step (.npy; tests)")
@@ -409,11 +447,14 @@ def main():
     if args.dump_frame and rank == 0:
         import numpy as np
         np.save(args.dump_frame, accum.cpu().numpy())
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, accum.cpu().numpy(),
+                     [s.samples, s.closest_hit_rays, s.shadow_rays, s.traced_rays[0], s.traced_rays[1]])
 
     # The north star's own scene (BASELINE configs[3], C4: ~250k triangles, 1080p, 256 spp), timed on
-    # the same ranks with the same sharding: one warm-up frame, then --c4-steps frames.
+    # the same ranks with the same sharding: one warm-up frame, then --c4-steps frames.  --full only.
     c4 = None
-    if args.c4_steps > 0 and args.config != "c4" and args.shard_of <= 1:
+    if args.full and args.c4_steps > 0 and args.config != "c4" and args.shard_of <= 1:
         c4scene, c4dev, c4st, _, c4acc, c4step = setup("c4", CONFIGS["c4"]["w"], CONFIGS["c4"]["h"], asset_dir)
         # C4's roofline is the trace launch's (k_trace, the kernel with the most GPU time there): HIP
         # events around the extend launches only, in the warm-up and the timed frames
@@ -540,28 +581,30 @@ def main():
         concurrency = sum(ref[:5]) / (elapsed * 1e3 / args.steps) if elapsed > 0 else 0.0
         pipe_bytes = PIPE_BYTES_PER_RAY * (closest + shadow) + PIPE_BYTES_PER_SAMPLE * samples
         pipe_gbs = pipe_bytes / elapsed / 1e9
-        # output pass on the resolved frame: k_post, 16 B read + 4 B written per pixel
-        bgra = torch.empty((h, w), dtype=torch.int32, device=f"cuda:{device}")
-        pcall = lambda: rt.lib().rt_postprocess_device(device, C.c_void_p(accum.data_ptr()), w, h, C.byref(post), 0,
-                                                       C.c_void_p(bgra.data_ptr()), C.c_void_p(stream.cuda_stream))
-        for _ in range(3):
-            assert pcall() == 0, rt.lib().rt_last_error()
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        post_ms = []
-        for _ in range(20):
-            ev[0].record(stream)
-            assert pcall() == 0
-            ev[1].record(stream)
-            ev[1].synchronize()
-            post_ms.append(ev[0].elapsed_time(ev[1]))
-        post_ms = sorted(post_ms)[len(post_ms) // 2]
-        post_gbs = 20.0 * w * h / (post_ms * 1e-3) / 1e9
-        postprocess = {"kernel": "k_post", "ms": round(post_ms, 4), "achieved_GBps": round(post_gbs, 1),
-                       "frac_of_hbm_peak": round(post_gbs / HBM_PEAK_GBS, 4), "bytes_per_pixel": 20,
-                       "note": "median of 20 calls, HIP events on the render stream around each call "
-                               "(includes launch latency); rocprof gives the kernel alone"}
+        # output pass on the resolved frame (--full): k_post, 16 B read + 4 B written per pixel
+        postprocess = None
+        if args.full:
+            bgra = torch.empty((h, w), dtype=torch.int32, device=f"cuda:{device}")
+            pcall = lambda: rt.lib().rt_postprocess_device(device, C.c_void_p(accum.data_ptr()), w, h, C.byref(post), 0,
+                                                           C.c_void_p(bgra.data_ptr()), C.c_void_p(stream.cuda_stream))
+            for _ in range(3):
+                assert pcall() == 0, rt.lib().rt_last_error()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            post_ms = []
+            for _ in range(20):
+                ev[0].record(stream)
+                assert pcall() == 0
+                ev[1].record(stream)
+                ev[1].synchronize()
+                post_ms.append(ev[0].elapsed_time(ev[1]))
+            post_ms = sorted(post_ms)[len(post_ms) // 2]
+            post_gbs = 20.0 * w * h / (post_ms * 1e-3) / 1e9
+            postprocess = {"kernel": "k_post", "ms": round(post_ms, 4), "achieved_GBps": round(post_gbs, 1),
+                           "frac_of_hbm_peak": round(post_gbs / HBM_PEAK_GBS, 4), "bytes_per_pixel": 20,
+                           "note": "median of 20 calls, HIP events on the render stream around each call "
+                                   "(includes launch latency); rocprof gives the kernel alone"}
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(rt, cfg, args.spp, args.cpu_seconds)
         parallelism = (f"{args.shard_mode}%{args.shard_of} (rank {args.shard_index} only, diagnostic)"
                        if args.shard_of > 1 else f"{args.shard_mode}%{world}" +

@@ -45,6 +45,32 @@ def test_traffic_table(bench):
         assert upf["k_shade"] > 0 and upf[kernels[cfg][2]] > 0
 
 
+def test_dump_outputs(bench, tmp_path, monkeypatch):
+    """--dump-outputs: a frame within the size limit whole, a larger one as the same seeded pixel
+    sample every time; float32 / float64 files, within the limit in all."""
+    import numpy as np
+    frame = np.arange(7 * 5 * 4, dtype=np.float32).reshape(7, 5, 4)
+    counts = [35, 120, 40, 100, 30]
+    bench.dump_outputs(str(tmp_path / "whole"), frame, counts)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["counts.npy", "frame.npy"]
+    got = np.load(tmp_path / "whole" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+    c = np.load(tmp_path / "whole" / "counts.npy")
+    assert c.dtype == np.float64 and c.tolist() == counts
+    assert bench.DUMP_BYTES <= 60 * 10**6
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 40 + 10 * 24)         # the counts and ten pixels with their indices
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), frame, counts)
+    assert sorted(os.listdir(tmp_path / "a")) == ["counts.npy", "frame_sample.npy", "frame_sample_index.npy"]
+    px, idx = np.load(tmp_path / "a" / "frame_sample.npy"), np.load(tmp_path / "a" / "frame_sample_index.npy")
+    assert px.dtype == np.float32 and idx.dtype == np.float64 and px.shape == (10, 4) and idx.shape == (10,)
+    assert np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < 35
+    assert np.array_equal(px, frame.reshape(-1, 4)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "frame_sample_index.npy"))
+    assert px.nbytes + idx.nbytes + 40 <= 40 + 10 * 24
+
+
 def test_host_cores(bench):
     """The CPU baseline's thread count is the cores this process may use: the affinity mask capped
     by the cgroup CPU quota, never more than os.cpu_count()."""

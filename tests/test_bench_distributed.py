@@ -25,7 +25,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--config", "c3", "--width", "320", "--height", "200", "--spp", "16", "--steps", "2", "--warmup", "1",
-        "--no-cpu-baseline", "--c4-steps", "1"]
+        "--full", "--no-cpu-baseline", "--c4-steps", "1"]      # --full: the C4 frames the tests compare
 
 
 def _free_port():
@@ -94,7 +94,8 @@ def test_bench_rccl_one_rank(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONUNBUFFERED="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    plain = _run([sys.executable, "bench.py", "--gpus", "1"] + ARGS + ["--dump-frame", str(tmp_path / "plain.npy")], env)
+    plain = _run([sys.executable, "bench.py", "--gpus", "1"] + ARGS + ["--dump-frame", str(tmp_path / "plain.npy"),
+                                                                      "--dump-outputs", str(tmp_path / "out")], env)
     rccl = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                  "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "1",
                  "--dist-backend", "nccl", "--force-dist"] + ARGS + ["--dump-frame", str(tmp_path / "rccl.npy")], env)
@@ -113,3 +114,10 @@ def test_bench_rccl_one_rank(tmp_path):
     assert (rccl["c4"]["closest_hit_rays"], rccl["c4"]["shadow_rays"]) == (plain["c4"]["closest_hit_rays"],
                                                                            plain["c4"]["shadow_rays"])
     assert np.array_equal(f1, f2)
+    # --dump-outputs: the last timed step's frame and counts (the steps are identical frames)
+    out = np.load(tmp_path / "out" / "frame.npy")
+    counts = np.load(tmp_path / "out" / "counts.npy")
+    assert out.dtype == np.float32 and np.array_equal(out, f1)
+    assert counts.dtype == np.float64
+    assert (counts[1] * plain["steps"], counts[2] * plain["steps"]) == (plain["closest_hit_rays"], plain["shadow_rays"])
+    assert [c * plain["steps"] for c in counts[3:5]] == plain["traced_rays"]

@@ -151,12 +151,26 @@ def test_cancel_mid_frame(rt):
     scene, cam, st, fc, post = rt.load_preset("c3", 1920, 1080)
     st.samples_per_pixel = 1024                      # ~1.2 s: the cancel lands mid-frame
     dev = rt.DeviceScene(scene, 0)
+    returned = threading.Event()
+
+    def cancel_until_returned():
+        # A frame clears the flag when its wavefront loop starts, after it has allocated its pools: how
+        # long that takes depends on the box, so a single rt_cancel at a fixed delay may come too early
+        # and be lost.  Repeated every 10 ms it lands inside the ~1.2 s loop wherever that starts.
+        returned.wait(0.15)
+        while not returned.is_set():
+            dev.cancel()
+            returned.wait(0.01)
+
     try:
-        timer = threading.Timer(0.15, dev.cancel)
-        timer.start()
-        with pytest.raises(rt.RenderError) as ei:
-            dev.render(cam, st, fc, 1920, 1080)
-        timer.join()
+        canceller = threading.Thread(target=cancel_until_returned)
+        canceller.start()
+        try:
+            with pytest.raises(rt.RenderError) as ei:
+                dev.render(cam, st, fc, 1920, 1080)
+        finally:
+            returned.set()
+            canceller.join()
         assert ei.value.code == rt.abi.RT_ERROR_CANCELLED
         small = type(st).from_buffer_copy(st)
         small.samples_per_pixel = 16

@@ -16,7 +16,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q -p no:cacheprovider --time
 rc=$?; echo "pytest rc=$rc"; grep -E "passed|failed" $OUT/pytest_gpu.log | tail -1
 cp gpurun_out/parity_report.json $OUT/parity_report.json 2>/dev/null
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 400 python bench.py > $OUT/bench.log 2>&1 || { echo "bench failed"; exit 1; }
+timeout -k 10 400 python bench.py --full > $OUT/bench.log 2>&1 || { echo "bench failed"; exit 1; }
 tail -1 $OUT/bench.log | cut -c1-300
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $PWD/$OUT/prof -o run -- \
     python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/prof.log 2>&1 || { echo "rocprof failed"; exit 1; }

@@ -14,7 +14,7 @@ timeout -k 10 1000 python -u -m pytest tests -m gpu -v -p no:cacheprovider --tim
 rc=$?; echo "pytest rc=$rc"; grep -E "FAILED|passed|failed" $OUT/pytest_gpu.log | tail -5
 cp gpurun_out/parity_report.json $OUT/parity_report.json 2>/dev/null
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 400 python bench.py > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -5 $OUT/bench.log; exit 1; }
+timeout -k 10 400 python bench.py --full > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -5 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log | cut -c1-240
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $PWD/$OUT/prof_c3 -o run -- \
     python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --c4-steps 0 > $OUT/prof_c3.log 2>&1 || { echo "rocprof c3 failed"; exit 1; }

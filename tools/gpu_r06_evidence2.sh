@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/ev_r06b
 mkdir -p $OUT
-timeout -k 10 400 python bench.py > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -5 $OUT/bench.log; exit 1; }
+timeout -k 10 400 python bench.py --full > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -5 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log | cut -c1-200
 timeout -k 10 400 python bench.py --steps 20 --warmup 2 --no-cpu-baseline > $OUT/bench20.log 2>&1 || { echo "bench20 failed"; exit 1; }
 tail -1 $OUT/bench20.log | cut -c1-200
