@@ -27,7 +27,8 @@ from .abi import (V3, v3, M4x4Inv, Material, Camera, Settings, FilterCache, Post
 __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settings", "load_reconstruction_kernel",
            "translate", "scale", "rotate_x", "rotate_y", "rotate_z", "identity", "aim_camera", "aim_camera_at",
            "recompute_camera", "resolve_bgra8", "postprocess", "write_bitmap", "lib", "abi", "v3", "PI_32", "DEG_TO_RAD",
-           "set_splat_mode", "splat_mode", "take_picture", "read_bitmap"]
+           "set_splat_mode", "splat_mode", "take_picture", "read_bitmap", "integrator_name", "find_integrator",
+           "integrator_supported"]
 
 PI_32 = 3.14159265359
 DEG_TO_RAD = 6.28318530717 / 360.0
@@ -417,6 +418,25 @@ def take_picture(scene, camera, settings, filter_cache, post, w, h, spp, path, t
                                   C.byref(post), w, h, spp, total_frame_index, device, str(path).encode(),
                                   C.byref(stats)))
     return stats
+
+
+def integrator_name(integrator):
+    """rt_integrator_name: the reference's name of a g_integrators index (RT/integrators.cpp:823-830),
+    None when out of range."""
+    name = lib().rt_integrator_name(int(integrator))
+    return None if name is None else name.decode()
+
+
+def find_integrator(name):
+    """rt_find_integrator: the index of a name, 0 (the default integrator) when unknown, as the
+    reference's find_integrator (RT/integrators.cpp:835-845)."""
+    return int(lib().rt_find_integrator(str(name).encode()))
+
+
+def integrator_supported(integrator):
+    """rt_integrator_supported: True when the render entries take this integrator (Whitted and Ground
+    Truth Recursive are refused: they need a per-path recursion stack)."""
+    return bool(lib().rt_integrator_supported(int(integrator)))
 
 
 def device_count():

@@ -27,6 +27,10 @@ RT_SAMPLING_UNIFORM, RT_SAMPLING_OPTIMIZED_BLUE_NOISE, RT_SAMPLING_STRATIFIED = 
 RT_SPLAT_STREAM, RT_SPLAT_EXACT, RT_SPLAT_ATOMIC = range(3)          # rt_splat_mode
 RT_SHARD_TILES, RT_SHARD_PASSES = range(2)                           # rt_shard_mode
 RT_SHADOW_LAUNCH_AUTO, RT_SHADOW_LAUNCH_SEPARATE, RT_SHADOW_LAUNCH_MERGED = range(3)   # rt_shadow_launch (ABI 8)
+# rt_integrator: the reference's g_integrators table indices (RT/integrators.cpp:823-830)
+(RT_INTEGRATOR_ADVANCED, RT_INTEGRATOR_WHITTED, RT_INTEGRATOR_GROUND_TRUTH_RECURSIVE,
+ RT_INTEGRATOR_GROUND_TRUTH_ITERATIVE, RT_INTEGRATOR_NORMALS, RT_INTEGRATOR_DISTANCES) = range(6)
+RT_INTEGRATOR_COUNT = 6
 RT_RNG_PER_SAMPLE, RT_RNG_TILE_STREAM = 0, 1
 RT_HIT_MISS = 0xFFFFFFFF
 RT_HIT_PLANE_BIT = 0x80000000
@@ -193,6 +197,9 @@ ABI_FUNCTIONS = {
     "rt_abi_version": (C.c_int, []),
     "rt_last_error": (C.c_char_p, []),
     "rt_device_count": (C.c_int, [P(C.c_int)]),
+    "rt_integrator_name": (C.c_char_p, [C.c_int]),
+    "rt_find_integrator": (C.c_int, [C.c_char_p]),
+    "rt_integrator_supported": (C.c_int, [C.c_int]),
     "rt_scene_upload": (C.c_int, [P(SceneDesc), C.c_int, P(C.c_void_p)]),
     "rt_scene_free": (C.c_int, [C.c_void_p]),
     "rt_render": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,

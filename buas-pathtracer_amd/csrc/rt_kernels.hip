@@ -2141,8 +2141,69 @@ RT_D bool shade_bounce(const DevScene& sc, const rt_settings& st, const SamplerS
     return done;
 }
 
+// One bounce of the reference's single-chain integrators besides the Advanced one, in its operation
+// order.  INTEG (rt_integrator):
+//   RT_INTEGRATOR_GROUND_TRUTH_ITERATIVE (RT/integrators.cpp:498-538): no NEE, no MIS, no roulette; the hit's
+//     N as intersect_scene returns it (no inside flip, no material stack: eta_i is 1), one
+//     random_unilaterals draw per bounce, a mirror reflection with the throughput unchanged or a uniform
+//     hemisphere bounce (brdf, then dot(R, N), then 2 pi: three multiplies);
+//   RT_INTEGRATOR_NORMALS (:544-560), RT_INTEGRATOR_DISTANCES (:563-579): the camera ray's hit, then the path
+//     ends (the host runs them with a path life of 1 whatever max_bounce_count says).
+// No shadow ray, no sample_1d / sample_2d draw, and pool.mstack is never touched.  Returns true when the
+// path ends.
+template <int INTEG>
+RT_D bool shade_bounce_gt(const DevScene& sc, const rt_settings& st, const Hit& h, V3& ro, V3& rd, V3& thr,
+                          V3& total, uint32_t& bounce, Rng& rng) {
+    constexpr bool FIRST_HIT = INTEG == RT_INTEGRATOR_NORMALS || INTEG == RT_INTEGRATOR_DISTANCES;
+    if (h.code == RT_HIT_MISS) {
+        if (FIRST_HIT) total = sample_sky(sc, rd);                          // :558, :577
+        else total = add(total, mul(thr, sample_sky(sc, rd)));              // :535
+        return true;
+    }
+    if (INTEG == RT_INTEGRATOR_DISTANCES) {
+        total = v3s(1.0f - clampf_(h.t / 15.0f, 0.0f, 1.0f));               // :575
+        return true;
+    }
+    V3 I, N;
+    uint32_t surf_id;
+    Ray ray; ray.o = ro; ray.d = rd;
+    hit_geometry(sc, ray, h, I, N, surf_id);
+    if (INTEG == RT_INTEGRATOR_NORMALS) {
+        total = smul(0.5f, add(v3s(1.0f), N));                              // :556
+        return true;
+    }
+    const rt_material m = sc.materials[surf_id];
+    if (m.flags & RT_MATERIAL_EMISSIVE) {                                   // :507-510
+        total = add(total, mul(thr, rv3(m.emission_color)));
+        return true;
+    }
+    float r0, r1, r2, r3;
+    unilaterals(rng, r0, r1, r2, r3);                                       // :512
+    (void)r3;
+    const float eta_i = 1.0f, eta_t = m.ior;
+    const float eta = eta_i / eta_t;
+    const float cos_i = -dot(rd, N);
+    float cos_t;
+    const float refl = fresnel_dielectric(cos_i, eta_i, eta_t, eta, cos_t);
+    if (r0 < refl) {                                                        // make_reflected_ray :267-270
+        const V3 nd = reflect(rd, N);
+        ro = add(I, muls(nd, EPSILON)); rd = nd;
+    } else {                                                                // :525-532
+        const V3 brdf = muls(evaluate_material(m, I), 1.0f / PI_32);
+        thr = mul(thr, brdf);
+        const V3 R = map_to_hemisphere(N, V2{r1, r2});
+        ro = add(I, muls(N, EPSILON)); rd = R;
+        thr = muls(thr, dot(R, N));
+        thr = muls(thr, 2.0f*PI_32);
+    }
+    ++bounce;
+    return bounce >= st.max_bounce_count;
+}
+
 // ENV: rt_set_env_sampling on, the scene has an environment map and NEE is on
-template <bool IN_LDS, bool ENV>
+// INTEG: the rt_integrator the bounce is one of (shade_bounce, or shade_bounce_gt for the others, which
+// queue no shadow ray: their instantiations drop the NEE staging below)
+template <bool IN_LDS, bool ENV, int INTEG = RT_INTEGRATOR_ADVANCED>
 __global__ void __launch_bounds__(BLOCK) RT_SHADE_ATTR k_shade(DevScene sc_g, rt_settings st, FrameParams fp, Pool pool,
                                                  Counters* cnt, int cur, int sparse, int fuse) {
     if (fuse && cnt->fused) return;                 // k_drain runs this iteration's paths (uniform)
@@ -2163,7 +2224,15 @@ __global__ void __launch_bounds__(BLOCK) RT_SHADE_ATTR k_shade(DevScene sc_g, rt
         h4 = ldnt(&pool.hit[slot]); r4 = ldnt(&pool.rng[slot]); hw = ldnt(&pool.hit_w[slot]);
     };
     if (sparse) {
-        if (cnt->done) return;                                          // uniform: every block reads it
+        if (cnt->done) {                                                // uniform: every block reads it
+            // Without a fused drain nothing retires the pool (k_drain_list), and the host has iterations in
+            // flight behind the bookkeep that found the partition complete.  A k_shade that leaves here writes
+            // no finished count, so this parity's finished set would stay as the last k_shade that finished
+            // paths left it, splatted already, and the k_generate after next would splat it again (float
+            // atomics: added twice; records: rewritten alike).  Empty it.
+            if (INTEG != RT_INTEGRATOR_ADVANCED && slot < pool.n && (slot & 63u) == 0) pool.fin_w[slot >> 6] = 0;
+            return;
+        }
         if (slot < pool.n) {
             state0 = pool.state[slot];
             if (state0 != S_FREE) load_path();
@@ -2212,8 +2281,11 @@ __global__ void __launch_bounds__(BLOCK) RT_SHADE_ATTR k_shade(DevScene sc_g, rt
         SamplerState ss = {px, py, canonical, st.sampling_strategy};
         Hit h;
         h.t = h4.x; h.code = __float_as_uint(h4.y); h.tri = __float_as_uint(h4.z); h.v = h4.w; h.w = hw;
-        done = shade_bounce<ENV>(sc, st, ss, pool, slot, h, ro, rd, thr, total, prev_pdf, bounce, is_spec, at, rng,
-                                 cast_shadow, sh_o, sh_d, sh_c, sh_t, sh_light);
+        if constexpr (INTEG == RT_INTEGRATOR_ADVANCED)
+            done = shade_bounce<ENV>(sc, st, ss, pool, slot, h, ro, rd, thr, total, prev_pdf, bounce, is_spec, at, rng,
+                                     cast_shadow, sh_o, sh_d, sh_c, sh_t, sh_light);
+        else
+            done = shade_bounce_gt<INTEG>(sc, st, h, ro, rd, thr, total, bounce, rng);
         // The survivor's state that the two prologues below do not change goes out now, so the
         // throughput, RNG and flags are not held in registers across them (total_color and the
         // hit record follow the prologues).  The wave's paths that continue go, in slot order, to
@@ -3460,9 +3532,36 @@ Pool pool_view(const Pool& p, int par) {
     return v;
 }
 
+// The reference's integrator table (g_integrators, RT/integrators.cpp:823-830), by rt_integrator
+const char* const INTEGRATOR_NAMES[RT_INTEGRATOR_COUNT] = {
+    "Advanced Pathtracer", "Whitted", "Ground Truth Recursive", "Ground Truth Iterative", "Normals", "Distances",
+};
+inline bool integrator_on_device(int i) {
+    return i == RT_INTEGRATOR_ADVANCED || i == RT_INTEGRATOR_GROUND_TRUTH_ITERATIVE || i == RT_INTEGRATOR_NORMALS ||
+           i == RT_INTEGRATOR_DISTANCES;
+}
+inline bool integrator_first_hit(int i) { return i == RT_INTEGRATOR_NORMALS || i == RT_INTEGRATOR_DISTANCES; }
+
+// The settings the kernels and the schedule see.  Normals and Distances never read max_bounce_count
+// (RT/integrators.cpp:544-579): they trace their camera ray even when it is 0, and their path ends at that
+// hit.  With a bounce limit of 1 k_generate casts the ray, k_bookkeep counts it (ResPlan::cast0) and the
+// record ring is sized for a path life of one iteration.
+rt_settings device_settings(const rt_settings& st) {
+    rt_settings e = st;
+    if (integrator_first_hit(st.integrator)) e.max_bounce_count = 1;
+    return e;
+}
+
 int check_inputs(const rt_settings* st, const rt_filter_cache* f) {
     if (!st || !f) { set_error("null settings/filter"); return RT_ERROR_INVALID; }
-    if (st->integrator != RT_INTEGRATOR_ADVANCED) { set_error("only the Advanced Pathtracer integrator is on the device path"); return RT_ERROR_INVALID; }
+    if (st->integrator < 0 || st->integrator >= RT_INTEGRATOR_COUNT) { set_error("bad integrator"); return RT_ERROR_INVALID; }
+    if (!integrator_on_device(st->integrator)) {
+        // Whitted branches in a medium and both fold their results on the way back up the recursion
+        // (RT/integrators.cpp:391-392, :417-426, :474-483): not reproducible by a forward wavefront
+        set_error(std::string("the ") + INTEGRATOR_NAMES[st->integrator] +
+                  " integrator needs a per-path recursion stack and is not on the device path");
+        return RT_ERROR_INVALID;
+    }
     if (st->max_bounce_count > 63) { set_error("max_bounce_count > 63 overruns the 64-entry material stack"); return RT_ERROR_INVALID; }
     if (st->use_path_guide) { set_error("use_path_guide is dead code in the reference and unsupported"); return RT_ERROR_INVALID; }
     if (st->sampling_strategy < 0 || st->sampling_strategy > 2) { set_error("bad sampling_strategy"); return RT_ERROR_INVALID; }
@@ -3541,6 +3640,12 @@ void launch_resolve_tiles(const SplatCfg& sp, const FrameParams& fp, const Pool&
 int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long long total, hipStream_t stream,
               const SplatCfg& sp, rt_stats* stats, bool shard) {
     auto t0 = std::chrono::steady_clock::now();
+    // st: device_settings() of the caller's.  The integrators besides the Advanced one have no NEE: they
+    // queue no shadow ray, so no connect launch is made (the frame runs the separate schedule without it),
+    // the environment NEE is off whatever rt_set_env_sampling says, and the fused drain (k_drain runs
+    // shade_bounce) stays off: their paths drain through k_shade.
+    const int integ = st->integrator;
+    const bool advanced = integ == RT_INTEGRATOR_ADVANCED;
     const bool listed = fp.list_xy != nullptr;
     const FrameShape shape = frame_shape(s, total, listed ? 0u : sp.passes);
     const int nparts = shape.nparts;
@@ -3570,7 +3675,7 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
     // pool if more (r02 sweeps: rank 0 of 8, 3.3M-path pools: 1x the lanes 40.5 ms, 2.5x 39.3, 4.5x 40.0,
     // 9x 41.0; the full frame's 8.4M-path pools: 2.5x 235.8, 600k 234.1-235.2, 1M 234.2-234.3 ms);
     // rt_scene_config::fuse_paths another count (0 = never)
-    const uint32_t fuse_paths = s->cfg.fuse_paths >= 0
+    const uint32_t fuse_paths = !advanced ? 0u : s->cfg.fuse_paths >= 0
         ? (uint32_t)std::min<int64_t>(s->cfg.fuse_paths, 0xFFFFFFFFll)
         : std::max(s->drain_lanes_full*5u/2u, pool_n / 10u);
     for (int k = 0; k < nparts; ++k) {
@@ -3646,9 +3751,10 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
     // instead of 75 % +1.4..+3.3 %; then 37 % +0.4..+1.7 % and 31 % +0.1..+1.2 % over 50 %, 25 % -1.1..-2.0 %;
     // a grid by sqrt(pool / 8.4M) also gave a share of 4 (6.6M paths, 67 %) -0.6..0 %.
     const uint32_t tgrid = (s->grid_by_pool && pool_n < BK_LARGE_POOL) ? std::max(1u, s->trace_grid/2u) : s->trace_grid;
-    const bool merged = s->cfg.shadow_launch == RT_SHADOW_LAUNCH_MERGED ||
+    const bool merged = advanced && (s->cfg.shadow_launch == RT_SHADOW_LAUNCH_MERGED ||
                         (s->cfg.shadow_launch == RT_SHADOW_LAUNCH_AUTO &&
-                         (shard || pool_n < BK_LARGE_POOL || s->shadow_share >= SHADOW_SHARE_MERGED));
+                         (shard || pool_n < BK_LARGE_POOL || s->shadow_share >= SHADOW_SHARE_MERGED)));
+    const bool connect = advanced && !merged;       // a shadow-ray launch of its own after k_shade
     auto plan_of = [&](int k, uint32_t mode) {
         const Run& r = run[k];
         // merged: a path's record is written two iterations after its last bounce (its shadow ray rides in the
@@ -3669,7 +3775,7 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
             const int slot = (int)((r.chunk_first[b] + i) % EV_SLOTS);
             for (int kern = 0; kern < RT_KERNEL_COUNT; ++kern) {
                 // (the splat runs inside k_generate; merged, the shadow rays inside k_trace: no events of their own)
-                if (!((prof >> kern) & 1u) || kern == RT_KERNEL_SPLAT || (merged && kern == RT_KERNEL_CONNECT)) continue;
+                if (!((prof >> kern) & 1u) || kern == RT_KERNEL_SPLAT || (!connect && kern == RT_KERNEL_CONNECT)) continue;
                 if (kern == RT_KERNEL_RESOLVE && !r.res_ev[slot]) continue;
                 float ms = 0.0f;
                 if (hipEventElapsedTime(&ms, ev(k, slot, kern, 0), ev(k, slot, kern, 1)) == hipSuccess) {
@@ -3684,7 +3790,7 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
     const bool ref = s->cfg.traversal_ref > 0;
     DevScene ds = s->ds;
     if (ref) { ds.top_seq = nullptr; ds.top_seq_len = 0; ds.listed_only = 0; }
-    const bool env = (s->cfg.env_sampling >= 0 ? s->cfg.env_sampling : g_env_sampling) && s->ds.env_tab &&
+    const bool env = advanced && (s->cfg.env_sampling >= 0 ? s->cfg.env_sampling : g_env_sampling) && s->ds.env_tab &&
                      st->next_event_estimation;
     auto iterate = [&](int k, bool plan) {
         Partition& pt = s->part[k];
@@ -3734,7 +3840,18 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
             }
         }
         b(RT_KERNEL_SHADE);
-        if (env) {
+        auto shade_gt = [&](auto tag) {                  // shade_bounce_gt<INTEG>: no environment NEE, no drain
+            constexpr int INTEG = decltype(tag)::value;
+            if (ds.blob_q) k_shade<true, false, INTEG><<<r.grid, BLOCK, 16*ds.blob_q, q>>>(ds, *st, fp, pv, pt.cnt, r.cur, sparse, fuse);
+            else k_shade<false, false, INTEG><<<r.grid, BLOCK, 0, q>>>(ds, *st, fp, pv, pt.cnt, r.cur, sparse, fuse);
+        };
+        if (integ == RT_INTEGRATOR_GROUND_TRUTH_ITERATIVE) {
+            shade_gt(std::integral_constant<int, RT_INTEGRATOR_GROUND_TRUTH_ITERATIVE>{});
+        } else if (integ == RT_INTEGRATOR_NORMALS) {
+            shade_gt(std::integral_constant<int, RT_INTEGRATOR_NORMALS>{});
+        } else if (integ == RT_INTEGRATOR_DISTANCES) {
+            shade_gt(std::integral_constant<int, RT_INTEGRATOR_DISTANCES>{});
+        } else if (env) {
             if (ds.blob_q) k_shade<true, true><<<r.grid, BLOCK, 16*ds.blob_q, q>>>(ds, *st, fp, pv, pt.cnt, r.cur, sparse, fuse);
             else k_shade<false, true><<<r.grid, BLOCK, 0, q>>>(ds, *st, fp, pv, pt.cnt, r.cur, sparse, fuse);
         } else if (ds.blob_q) {
@@ -3743,7 +3860,7 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
             k_shade<false, false><<<r.grid, BLOCK, 0, q>>>(ds, *st, fp, pv, pt.cnt, r.cur, sparse, fuse);
         }
         e(RT_KERNEL_SHADE);
-        if (!merged) {
+        if (connect) {
             // separate: this k_shade's shadow rays now; their NEE terms go to the survivors in the other
             // buffer and to this iteration's finished set, and the queue is the one of this parity
             Pool pc = pv;
@@ -3885,7 +4002,9 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
             for (int i = 0; i < 2*TV_N; ++i) tv[i] += c.trav[sh][i];
         iters = std::max(iters, run[k].iters);
     }
-    if (sum.traced_rays[0]) s->shadow_share = (double)sum.traced_rays[1] / (double)sum.traced_rays[0];
+    // (the Advanced integrator's frames only: a frame of an integrator without NEE says nothing about the
+    // next Advanced frame's shadow rays, and its zero would flip that frame's AUTO schedule)
+    if (advanced && sum.traced_rays[0]) s->shadow_share = (double)sum.traced_rays[1] / (double)sum.traced_rays[0];
     // TraversalStats per kind (rt_stats::traversal, rt_abi.h)
     rt_traversal_stats ts[2] = {};
     uint64_t steps[2] = {};
@@ -4124,6 +4243,17 @@ int rt_scene_set_config(rt_scene* s, const rt_scene_config* c) {
 }
 
 int rt_abi_version(void) { return RT_ABI_VERSION; }
+
+const char* rt_integrator_name(int integrator) {
+    return integrator >= 0 && integrator < RT_INTEGRATOR_COUNT ? INTEGRATOR_NAMES[integrator] : nullptr;
+}
+int rt_find_integrator(const char* name) {          // find_integrator (RT/integrators.cpp:835-845): unknown = the default
+    if (!name) return RT_INTEGRATOR_ADVANCED;
+    for (int i = 0; i < RT_INTEGRATOR_COUNT; ++i)
+        if (0 == strcmp(name, INTEGRATOR_NAMES[i])) return i;
+    return RT_INTEGRATOR_ADVANCED;
+}
+int rt_integrator_supported(int integrator) { return integrator_on_device(integrator) ? 1 : 0; }
 const char* rt_last_error(void) { return g_error.c_str(); }
 
 int rt_device_count(int* out) {
@@ -4561,6 +4691,8 @@ int rt_render_device(rt_scene* s, const rt_camera* camera, const rt_settings* st
     if (!s || !camera || !tiles || !d_pixels || !w || !h) { set_error("null argument"); return RT_ERROR_INVALID; }
     int err = check_inputs(st, filter);
     if (err) return err;
+    const rt_settings dev_st = device_settings(*st);
+    st = &dev_st;
     if (!tiles->tile_w || !tiles->tile_h || !tiles->shard_count || tiles->shard_index >= tiles->shard_count) {
         set_error("bad tile set"); return RT_ERROR_INVALID;
     }
@@ -4894,6 +5026,8 @@ int rt_trace_samples(rt_scene* s, const rt_camera* camera, const rt_settings* st
     rt_filter_cache box = {};
     int err = check_inputs(st, &box);
     if (err) return err;
+    const rt_settings dev_st = device_settings(*st);
+    st = &dev_st;
     if (!s || !camera || !pixel_xy || !sample_offset || !out || !w || !h || !tile_w || !tile_h) { set_error("null argument"); return RT_ERROR_INVALID; }
     if (!count) return RT_OK;
     if (w > 65535 || h > 65535) { set_error("frame larger than 65535 pixels a side"); return RT_ERROR_INVALID; }

@@ -136,9 +136,20 @@ enum rt_sampling_strategy {                                    /* RT/samplers.h:
     RT_SAMPLING_STRATIFIED           = 2,
 };
 
-enum rt_integrator {                                           /* g_integrators RT/integrators.cpp:823 */
-    RT_INTEGRATOR_ADVANCED = 0,   /* "Advanced Pathtracer" — the only one on the hot path */
+enum rt_integrator {                                           /* g_integrators RT/integrators.cpp:823-830, by table index */
+    RT_INTEGRATOR_ADVANCED               = 0,   /* "Advanced Pathtracer" (:581-821): NEE, MIS, roulette, media */
+    RT_INTEGRATOR_WHITTED                = 1,   /* "Whitted" (:417-426): not on the device (see below)          */
+    RT_INTEGRATOR_GROUND_TRUTH_RECURSIVE = 2,   /* "Ground Truth Recursive" (:474-483): not on the device       */
+    RT_INTEGRATOR_GROUND_TRUTH_ITERATIVE = 3,   /* "Ground Truth Iterative" (:486-541): brute-force path tracer */
+    RT_INTEGRATOR_NORMALS                = 4,   /* "Normals" (:544-560): first hit, 0.5*(1 + N)                 */
+    RT_INTEGRATOR_DISTANCES              = 5,   /* "Distances" (:563-579): first hit, 1 - saturate(t/15)        */
+    RT_INTEGRATOR_COUNT                  = 6,
 };
+/* The render entries take 0, 3, 4 and 5.  Whitted and Ground Truth Recursive fold their results on the way
+ * back up a recursion (Whitted also branches in a medium), which a forward wavefront cannot reproduce without
+ * a per-path recursion stack: they return RT_ERROR_INVALID by name.  Ground Truth Iterative, Normals and
+ * Distances cast no shadow rays (rt_stats::shadow_rays == 0) and ignore rt_set_env_sampling; Normals and
+ * Distances trace their one camera ray whatever max_bounce_count says, as the reference's do. */
 
 typedef struct rt_settings {                                   /* RT/scene.h:64-82 */
     int32_t  next_event_estimation;
@@ -292,6 +303,14 @@ typedef struct rt_scene rt_scene;   /* device-resident scene (opaque) */
 int         rt_abi_version(void);
 const char* rt_last_error(void);
 int         rt_device_count(int* out_count);
+
+/* The reference's integrator table (g_integrators, RT/integrators.cpp:823-830).  rt_integrator_name: the
+ * name its UI lists for a table index, NULL when out of range.  rt_find_integrator: the index of a name,
+ * 0 (the default integrator) when unknown, as find_integrator (:835-845).  rt_integrator_supported: 1 when
+ * the render entries take the index, else 0.  None needs a device. */
+const char* rt_integrator_name(int integrator);
+int         rt_find_integrator(const char* name);
+int         rt_integrator_supported(int integrator);
 
 /* Upload a flattened scene to `device` (create_scene_bvh must have run on
  * the host: RT/scene.cpp:173-242).  The device copy is owned by *out. */
