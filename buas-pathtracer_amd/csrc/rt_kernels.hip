@@ -1663,27 +1663,87 @@ RT_D V2 sample_jitter(const DevScene& sc, const rt_settings& st, const FramePara
 // gives k_generate 102 (a 128-SGPR wave, as many as a trace wave); capped at 80 it needs 78 with no
 // spills (96 per wave), so a generate wave finds room beside the trace waves sooner: a rank's share
 // of 8 +1.4 %, C3 / C4 +0.1 / +0.2 % (profiles/r04_sgpr_ab.txt)
+//
+// Dense waves (r07).  Each k_shade wave's survivors fill its first slots and the rest take new paths,
+// which claim consecutive sample numbers in slot order: claim_base[block] + the free slots of the
+// block's earlier waves + the rank among the wave's free slots.  A sample is keyed by its number, not
+// by its slot, so the wave that computes a claim need not be the wave that owns its slot: wave j of the
+// launch makes the claims [64j, 64j + 64) with all 64 lanes and writes each path to the slot the claim
+// maps to (claim_to_slot), the same slot as ever, so the pool's contents are what they were.  The waves
+// past the last claim skip the phase on a wave-uniform test; the slot-ordered form ran the whole
+// camera / sampler / prologue code in every wave with only its free lanes active.
+// The finished array is splatted the same way, compacted within the block (below).
+
+// The slot of a block's r-th free slot (r < f0 + f1 + f2 + f3, its four waves' free counts): each wave's
+// free slots are its last ones, and the claims run through them in slot order.
+static_assert(BLOCK == 256, "claim_slot: a k_shade block is four waves");
+__host__ __device__ inline uint32_t claim_slot(uint32_t b, uint32_t r, uint32_t f0, uint32_t f1, uint32_t f2, uint32_t f3) {
+    uint32_t w = 0, f = f0;
+    if (r >= f) { r -= f; w = 1; f = f1; }
+    if (w == 1 && r >= f) { r -= f; w = 2; f = f2; }
+    if (w == 2 && r >= f) { r -= f; w = 3; f = f3; }
+    return b*(uint32_t)BLOCK + w*64u + (64u - f) + r;
+}
+// One level of the 64-ary search for the block of a claim: the blocks [lo, lo + n) are probed at
+// lo + i*claim_stride(n), i < 64, and `hits` of the probed claim_base entries are <= the claim (the
+// first always is): the block lies in the range of the last such probe.
+__host__ __device__ inline uint32_t claim_stride(uint32_t n) { return (n + 63u) / 64u; }
+__host__ __device__ inline void claim_narrow(uint32_t& lo, uint32_t& n, uint32_t hits) {
+    const uint32_t stride = claim_stride(n), end = lo + n;
+    lo += (hits ? hits - 1u : 0u)*stride;
+    n = end - lo < stride ? end - lo : stride;
+}
+// The slots of the claims c0 + lane of a wave (c0 wave-uniform, every lane of the wave calls it; a lane
+// with `act` gets its slot).  The block of c0 comes from a cooperative 64-ary search over claim_base
+// (three dependent loads for C3's 8192 blocks; k_bookkeep, one workgroup on every partition's critical
+// chain, is left as it is), then the lanes find their own blocks among the next 64 bases with wave
+// shuffles, and again if the 64 claims span more blocks than that (blocks with next to nothing free).
+RT_D uint32_t claim_to_slot(const Pool& pool, uint32_t nblocks, uint32_t c0, uint32_t lane, bool act) {
+    uint32_t lo = 0, n = nblocks;
+    while (n > 64u) {                                                   // uniform
+        const uint32_t idx = lo + lane*claim_stride(n);
+        const uint32_t v = idx < lo + n ? pool.claim_base[idx] : 0xFFFFFFFFu;
+        claim_narrow(lo, n, (uint32_t)__popcll(__ballot(v <= c0)));
+    }
+    const uint32_t c = c0 + lane;
+    uint32_t b = 0;
+    bool found = !act;
+    for (uint32_t at = lo;; at += 64u) {                                // uniform; claim_base[at] <= c for the lanes left
+        const uint32_t idx = at + 1u + lane;
+        const uint32_t nb = idx < nblocks ? pool.claim_base[idx] : 0xFFFFFFFFu;   // the next blocks' first claims
+        uint32_t pos = 0;                                               // how many of them are <= c (they ascend)
+#pragma unroll
+        for (uint32_t step = 32u; step; step >>= 1)
+            if (__shfl(nb, (int)(pos + step - 1u)) <= c) pos += step;
+        if (__shfl(nb, 63) <= c) pos = 64u;
+        if (!found && pos < 64u) { b = at + pos; found = true; }
+        if (!__ballot(!found)) break;
+    }
+    if (b >= nblocks) b = nblocks - 1u;                                 // (counts that disagree with the scan: stay inside)
+    const uint4 f = reinterpret_cast<const uint4*>(pool.free_w)[b];
+    return claim_slot(b, c - pool.claim_base[b], f.x, f.y, f.z, f.w);
+}
+
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(80))) k_generate(DevScene sc_g, rt_settings st, FrameParams fp, Pool pool,
                                                         Counters* cnt, int cur) {
-    const uint32_t slot = blockIdx.x*blockDim.x + threadIdx.x;
-    const uint32_t lane = __lane_id(), wave = (slot >> 6) & (uint32_t)(BLOCK / 64 - 1);   // wave in the group
-    const uint32_t wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)(slot >> 6));
-    // Each wave's survivors fill its first slots; the rest take new paths, claiming consecutive
-    // sample numbers in slot order from the scan of the free counts k_bookkeep made (no atomics):
-    // the block's first claim, the free slots of the block's earlier waves, the lane's rank.
-    // The claim and the claimed sample's pixel are loaded first, so their round trips
-    // overlap the splat's below instead of waiting behind its stores.
-    const uint32_t first = 64u - pool.free_w[wbase];
-    uint32_t before = 0;
-    for (uint32_t w = 0; w < wave; ++w) before += pool.free_w[wbase - wave + w];
-    const bool want = lane >= first;
-    const uint32_t cbase = pool.claim_base[slot / BLOCK];
+    const uint32_t own = blockIdx.x*blockDim.x + threadIdx.x;           // the thread's own slot
+    const uint32_t lane = __lane_id(), wave = (own >> 6) & (uint32_t)(BLOCK / 64 - 1);   // wave in the group
+    const uint32_t wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)(own >> 6));
+    // G claims this iteration: the free slots k_bookkeep counted, or the samples left if fewer
     const unsigned long long remaining = remaining_samples(cnt);
-    const uint32_t claim = cbase + before + (lane - first);
-    // No sample left for this block to claim (the frame's drain): its free slots go idle
-    const bool none_left = (unsigned long long)cbase >= remaining;
-    const bool active = !none_left && want && (unsigned long long)claim < remaining;
-    const unsigned long long k = cnt->next_sample + claim;
+    const uint32_t gfree = cnt->gen_free;
+    const uint32_t G = remaining < (unsigned long long)gfree ? (uint32_t)remaining : gfree;
+    const uint32_t c0 = wbase*64u;                                      // this wave's claims: [c0, c0 + 64)
+    const bool gen = c0 < G;                                            // wave-uniform
+    // The claim's slot and the claimed sample's pixel are loaded first, so their round trips
+    // overlap the splat's below instead of waiting behind its stores.
+    bool active = gen && c0 + lane < G;
+    uint32_t slot = 0;
+    if (gen) {
+        slot = claim_to_slot(pool, pool.n / BLOCK, c0, lane, active);
+        active = active && slot < pool.n;
+    }
+    const unsigned long long k = cnt->next_sample + c0 + lane;
     uint32_t x = 0, y = 0, s = 0, p = 0;
     if (active) {
         if (fp.list_xy) {
@@ -1703,20 +1763,38 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(80))) k_
     }
     // The paths the k_shade two iterations back finished in this wave's slots (its finished array,
     // compacted): splat them.  Their last NEE contributions came in the k_trace in between.
-    if (lane < pool.fin_w[wbase]) {
-        const float4 fl = ldnt(&pool.fin_L[slot]);
-        const uint2 fk = ldnt(&pool.fin_k[slot]);
-        const uint32_t pixel = ldnt(&pool.fin_px[slot]);
-        const uint32_t fs = fp.list_xy ? fp.list_s[fk.x] : fk.x;
-        const V2 j = sample_jitter(sc_g, st, fp, pixel & 0xFFFFu, pixel >> 16, fs);
-        splat_sample(fp, pool, ld3(fl), fl.w, make_float2(j.x, j.y), fk.x, fk.y);
+    // They sit at the front of each wave's 64 entries; the block's four counts come in one 16-byte load,
+    // and wave w of the block splats the block's finished ranks [64w, 64w + 64) at their entries, so a
+    // block runs ceil(finished / 64) full splat rounds instead of four sparse ones.
+    {
+        const uint4 fw = reinterpret_cast<const uint4*>(pool.fin_w)[blockIdx.x];
+        uint32_t r = wave*64u + lane, w = 0;
+        const bool mine = r < fw.x + fw.y + fw.z + fw.w;
+        if (r >= fw.x) { r -= fw.x; w = 1; }
+        if (w == 1 && r >= fw.y) { r -= fw.y; w = 2; }
+        if (w == 2 && r >= fw.z) { r -= fw.z; w = 3; }
+        if (mine) {
+            const uint32_t e = blockIdx.x*(uint32_t)BLOCK + w*64u + r;
+            const float4 fl = ldnt(&pool.fin_L[e]);
+            const uint2 fk = ldnt(&pool.fin_k[e]);
+            const uint32_t pixel = ldnt(&pool.fin_px[e]);
+            const uint32_t fs = fp.list_xy ? fp.list_s[fk.x] : fk.x;
+            const V2 j = sample_jitter(sc_g, st, fp, pixel & 0xFFFFu, pixel >> 16, fs);
+            splat_sample(fp, pool, ld3(fl), fl.w, make_float2(j.x, j.y), fk.x, fk.y);
+        }
     }
-    if (none_left) {
-        if (want) pool.state[slot] = S_FREE;
-        return;
+    // The free slots that get no claim (nothing left to claim: the ring's claim limit, the frame's end,
+    // the retired pool after k_drain_list) go idle.  Slot-ordered, with the claim numbers of the
+    // slot-ordered form; skipped, wave-uniformly, in the iterations that fill every free slot.
+    if (G < gfree) {
+        const uint32_t first = 64u - pool.free_w[wbase];
+        uint32_t before = 0;
+        for (uint32_t w = 0; w < wave; ++w) before += pool.free_w[wbase - wave + w];
+        const uint32_t claim = pool.claim_base[blockIdx.x] + before + (lane - first);
+        if (lane >= first && (G == 0u || claim >= G)) pool.state[own] = S_FREE;
     }
+    if (!gen) return;
     const DevScene& sc = sc_g;       // nothing generate reads lives in the LDS copy of the scene
-    if (want && !active) pool.state[slot] = S_FREE;
     bool enqueue = false, cast = false;
     V3 nro = {0, 0, 0}, nrd = {0, 0, 0};
     Prologue pro = {};
@@ -1764,16 +1842,25 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(80))) k_
             enqueue = pro.bvh;
         }
     }
-    // new paths that enter the BVH go to the current extension queue: one returning atomic per wave,
-    // no barrier (r05, as in k_shade's tail)
-    const uint32_t shard = blockIdx.x % NSHARD;
-    const unsigned long long emask = __ballot(enqueue);
+    // New paths that enter the BVH go to the current extension queue, no barrier (r05, as in k_shade's
+    // tail).  A path is queued on the shard of its slot's block, as k_shade queues that block's survivors,
+    // so a shard still holds no more entries than its blocks have slots (Pool::shard_cap).  A wave's 64
+    // claims lie in one or two blocks unless next to nothing is free: the first lane of each shard in
+    // the wave adds that shard's count, all in one returning atomic instruction.
+    const uint32_t shard = (slot / BLOCK) % NSHARD;
+    unsigned long long emask = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < NSHARD; ++i) {
+        const unsigned long long m = __ballot(enqueue && shard == i);
+        if (shard == i) emask = m;
+    }
+    const uint32_t leader = emask ? (uint32_t)__ffsll((long long)emask) - 1u : 0u;
     const uint32_t wsum = __ockl_wfred_add_u32(pro.calls);
     uint32_t got = 0;
-    if (lane == 0 && emask) got = atomicAdd(&cnt->ext_count[cur][shard][0], (uint32_t)__popcll(emask));
-    if (lane == 1 && wsum) __hip_atomic_fetch_add(&cnt->trav[shard][TV_CALLS], (unsigned long long)wsum, __ATOMIC_RELAXED,
-                                                  __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t ebase = (uint32_t)__builtin_amdgcn_readlane((int)got, 0);
+    if (enqueue && lane == leader) got = atomicAdd(&cnt->ext_count[cur][shard][0], (uint32_t)__popcll(emask));
+    if (lane == 1 && wsum) __hip_atomic_fetch_add(&cnt->trav[blockIdx.x % NSHARD][TV_CALLS], (unsigned long long)wsum,
+                                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t ebase = __shfl(got, (int)leader);
     if (enqueue) {
         float4* q = pool.ext_rec[cur] + REC_Q*((size_t)shard*pool.shard_cap + ebase +
                                                (uint32_t)__popcll(emask & ((1ull << lane) - 1ull)));
@@ -5069,6 +5156,47 @@ int rt_debug_mesh_bvh4(const rt_bvh_node* nodes, uint32_t node_count, float* out
     *out_root_record = root;
     if (out && out_cap_nodes >= *out_nodes) memcpy(out, q.data(), q.size()*sizeof(float4));
     return (out && out_cap_nodes < *out_nodes) ? RT_ERROR_INVALID : RT_OK;
+}
+
+// k_generate's claim -> slot mapping on the host: k_bookkeep's scan of the blocks' free counts, then, per
+// wave of 64 claims, claim_to_slot's steps with the lanes as a loop (the same claim_stride / claim_narrow /
+// claim_slot functions, the same probes and rounds).
+int rt_debug_claim_slots(const uint32_t* free_w, uint32_t nwaves, uint32_t first_claim, uint32_t count, uint32_t* out_slots) {
+    if (!free_w || !nwaves || nwaves % (BLOCK / 64) || (count && !out_slots)) { set_error("invalid argument"); return RT_ERROR_INVALID; }
+    const uint32_t nblocks = nwaves / (BLOCK / 64);
+    std::vector<uint32_t> base(nblocks);
+    uint64_t run = 0;
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        base[b] = (uint32_t)run;
+        for (int w = 0; w < BLOCK / 64; ++w) {
+            if (free_w[4*b + w] > 64u) { set_error("a wave has at most 64 free slots"); return RT_ERROR_INVALID; }
+            run += free_w[4*b + w];
+        }
+    }
+    if ((uint64_t)first_claim + count > run) { set_error("more claims than free slots"); return RT_ERROR_INVALID; }
+    auto at_or_max = [&](uint32_t idx, uint32_t end) { return idx < end ? base[idx] : 0xFFFFFFFFu; };
+    for (uint32_t done = 0; done < count; done += 64u) {
+        const uint32_t c0 = first_claim + done, lanes = std::min(64u, count - done);
+        uint32_t lo = 0, n = nblocks;
+        while (n > 64u) {
+            uint32_t hits = 0;
+            for (uint32_t lane = 0; lane < 64u; ++lane) hits += at_or_max(lo + lane*claim_stride(n), lo + n) <= c0;
+            claim_narrow(lo, n, hits);
+        }
+        for (uint32_t lane = 0; lane < lanes; ++lane) {
+            const uint32_t c = c0 + lane;
+            uint32_t b = 0;
+            for (uint32_t at = lo;; at += 64u) {
+                uint32_t pos = 0;
+                for (uint32_t step = 32u; step; step >>= 1)
+                    if (at_or_max(at + 1u + pos + step - 1u, nblocks) <= c) pos += step;
+                if (at_or_max(at + 1u + 63u, nblocks) <= c) pos = 64u;
+                if (pos < 64u) { b = at + pos; break; }
+            }
+            out_slots[done + lane] = claim_slot(b, c - base[b], free_w[4*b], free_w[4*b + 1], free_w[4*b + 2], free_w[4*b + 3]);
+        }
+    }
+    return RT_OK;
 }
 
 int rt_debug_top_sequences(const rt_bvh_node* nodes, uint32_t node_count, uint32_t index_count,

@@ -374,6 +374,15 @@ int rt_debug_mesh_bvh4(const rt_bvh_node* nodes, uint32_t node_count, float* out
 int rt_debug_top_sequences(const rt_bvh_node* nodes, uint32_t node_count, uint32_t index_count,
                            float* out, uint32_t out_cap_entries, uint32_t* out_len);
 
+/* The claim -> slot mapping of the path generation (host only, no device needed).  A
+ * pool of `nwaves` waves of 64 slots (a multiple of 4: blocks of 256) where wave w's
+ * last free_w[w] (<= 64) slots are free: the new paths of an iteration claim the free
+ * slots in slot order.  Writes the slots of the claims [first_claim, first_claim +
+ * count), found the way the generate kernel finds them, in waves of 64 claims from
+ * first_claim on.  RT_ERROR_INVALID when the range passes the free slots. */
+int rt_debug_claim_slots(const uint32_t* free_w, uint32_t nwaves, uint32_t first_claim, uint32_t count,
+                         uint32_t* out_slots);
+
 /* Exhaustive check of the kernels' fast reciprocal (3 instructions instead of the
  * division expansion) against the correctly rounded IEEE 1.0f / x on `device`: every
  * one of the 2^32 bit patterns (NaNs compare equal as NaNs).  Writes the number of
