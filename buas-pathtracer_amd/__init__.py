@@ -28,7 +28,7 @@ __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settin
            "translate", "scale", "rotate_x", "rotate_y", "rotate_z", "identity", "aim_camera", "aim_camera_at",
            "recompute_camera", "resolve_bgra8", "postprocess", "write_bitmap", "lib", "abi", "v3", "PI_32", "DEG_TO_RAD",
            "set_splat_mode", "splat_mode", "take_picture", "read_bitmap", "integrator_name", "find_integrator",
-           "integrator_supported"]
+           "integrator_supported", "scene_integrator_supported"]
 
 PI_32 = 3.14159265359
 DEG_TO_RAD = 6.28318530717 / 360.0
@@ -184,6 +184,15 @@ class Scene:
     def set_sky(self, top, bot):
         lib().rth_set_sky(self._h, _v(top), _v(bot))
 
+    def set_ambient_light(self, ambient_light):
+        """Scene::ambient_light (RT/scene.h:102): added to the Whitted integrator's illumination only.
+        DeviceScene passes it on at upload."""
+        lib().rth_scene_set_ambient_light(self._h, _v(ambient_light))
+
+    def ambient_light(self):
+        a = lib().rth_scene_ambient_light(self._h)
+        return (a.x, a.y, a.z)
+
     def load_environment_map(self, path):
         if not lib().rth_load_environment_map(self._h, str(path).encode()):
             raise ValueError(lib().rth_last_error().decode())
@@ -238,6 +247,9 @@ class DeviceScene:
         h = C.c_void_p()
         _check(lib().rt_scene_upload(C.byref(scene.desc()), device, C.byref(h)))
         self._h = h
+        ambient = getattr(scene, "ambient_light", None)     # not part of rt_scene_desc; any object with desc() uploads
+        if ambient is not None:
+            self.set_ambient_light(ambient())
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -290,6 +302,21 @@ class DeviceScene:
 
     def cancel(self):
         lib().rt_cancel(self._h)
+
+    def set_recursive_integrators(self, enable=True):
+        """rt_scene_set_recursive_integrators: on, the render entries take Whitted and Ground Truth Recursive
+        for this scene (a frame stack is allocated on the device); off (the default), they refuse them."""
+        _check(lib().rt_scene_set_recursive_integrators(self._h, int(bool(enable))))
+
+    def integrator_supported(self, integrator):
+        """rt_scene_integrator_supported: integrator_supported plus Whitted and Ground Truth Recursive when
+        this scene has opted in."""
+        return bool(lib().rt_scene_integrator_supported(self._h, int(integrator)))
+
+    def set_ambient_light(self, ambient_light):
+        """rt_scene_set_ambient_light: Scene::ambient_light, read by the Whitted integrator only."""
+        a = _v(ambient_light)
+        _check(lib().rt_scene_set_ambient_light(self._h, C.byref(a)))
 
     def config(self):
         """rt_scene_get_config: this scene's schedule and splat settings (abi.SceneConfig)."""
@@ -437,6 +464,11 @@ def integrator_supported(integrator):
     """rt_integrator_supported: True when the render entries take this integrator (Whitted and Ground
     Truth Recursive are refused: they need a per-path recursion stack)."""
     return bool(lib().rt_integrator_supported(int(integrator)))
+
+
+def scene_integrator_supported(dev, integrator):
+    """rt_scene_integrator_supported for a DeviceScene, or None: then it equals integrator_supported."""
+    return bool(lib().rt_scene_integrator_supported(dev._h if dev is not None else None, int(integrator)))
 
 
 def device_count():

@@ -200,6 +200,9 @@ ABI_FUNCTIONS = {
     "rt_integrator_name": (C.c_char_p, [C.c_int]),
     "rt_find_integrator": (C.c_int, [C.c_char_p]),
     "rt_integrator_supported": (C.c_int, [C.c_int]),
+    "rt_scene_set_recursive_integrators": (C.c_int, [C.c_void_p, C.c_int]),
+    "rt_scene_integrator_supported": (C.c_int, [C.c_void_p, C.c_int]),
+    "rt_scene_set_ambient_light": (C.c_int, [C.c_void_p, P(V3)]),
     "rt_scene_upload": (C.c_int, [P(SceneDesc), C.c_int, P(C.c_void_p)]),
     "rt_scene_free": (C.c_int, [C.c_void_p]),
     "rt_render": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
@@ -252,6 +255,8 @@ HOST_FUNCTIONS = {
     "rth_mesh_bvh_info": (C.c_int, [C.c_void_p, C.c_uint32, P(BvhInfo)]),
     "rth_scene_bvh_info": (C.c_int, [C.c_void_p, P(BvhInfo)]),
     "rth_set_sky": (None, [C.c_void_p, V3, V3]),
+    "rth_scene_set_ambient_light": (None, [C.c_void_p, V3]),
+    "rth_scene_ambient_light": (V3, [C.c_void_p]),
     "rth_load_environment_map": (C.c_int, [C.c_void_p, C.c_char_p]),
     "rth_set_environment_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(V3)]),
     "rth_create_scene_bvh": (C.c_int, [C.c_void_p]),

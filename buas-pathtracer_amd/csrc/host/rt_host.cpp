@@ -291,6 +291,7 @@ struct rth_scene {
     std::vector<rt_bvh_node> bvh_nodes;
     std::vector<uint32_t> bvh_indices;
     rt_v3 top_sky = {0, 0, 0}, bot_sky = {0, 0, 0};
+    rt_v3 ambient_light = {0, 0, 0};                   // Scene::ambient_light RT/scene.h:102 (Whitted only)
     uint32_t sky_w = 0, sky_h = 0;
     std::vector<rt_v3> sky;
     std::vector<float> sky_cdf;
@@ -763,6 +764,8 @@ int rth_mesh_bvh_info(rth_scene* s, uint32_t mesh_id, rth_bvh_info* out) {
 int rth_scene_bvh_info(rth_scene* s, rth_bvh_info* out) { bvh_info(s->bvh_nodes, out); return 1; }
 
 void rth_set_sky(rth_scene* s, rt_v3 top, rt_v3 bot) { s->top_sky = top; s->bot_sky = bot; }
+void rth_scene_set_ambient_light(rth_scene* s, rt_v3 a) { if (s) s->ambient_light = a; }
+rt_v3 rth_scene_ambient_light(const rth_scene* s) { return s ? s->ambient_light : rt_v3{0, 0, 0}; }
 
 }  // extern "C"
 int rth_load_environment_map_bytes(rth_scene* s, std::vector<char>& file);

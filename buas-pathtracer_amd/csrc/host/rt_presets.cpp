@@ -137,6 +137,7 @@ void week_1(Ctx& c) {
     camera_basic(c, 60.0f, 0.0f, 1.0f);
     c.cam->p = v3(0, 4, -10); rth_aim_camera(c.cam, v3(0, 0, -1));
     c.st->lens_distortion = 0.0f; set_filter(c, "Box"); c.post->tonemapping = 0;
+    rth_scene_set_ambient_light(c.s, v3(PI_32));                           // :812, and week_2's :832
     uint32_t g = add_diffuse(c, v3(1), 1.0f, 0.0f, true, v3(0.0f));
     plane(c, g, v3(0, 1, 0), 0.0f);
 }
@@ -147,6 +148,7 @@ void week_2(Ctx& c) {
 }
 void week_3(Ctx& c) {
     week_2(c);
+    rth_scene_set_ambient_light(c.s, v3(0.0f));                            // week_3_scene sets none
     uint32_t lm = rth_add_emissive_material(c.s, v3(12500));
     sphere(c, lm, 0.1f, translate(v3(8, 16, -8)));
 }
@@ -167,6 +169,7 @@ void week_5(Ctx& c) {                                                      // :8
     c.st->lens_distortion = 0.0f; c.st->max_bounce_count = 12; c.st->caustics = 0;
     set_filter(c, "Gaussian 3"); c.post->tonemapping = 1;
     rth_set_sky(c.s, v3(0.1f, 0.7f, 2.0f), v3(0.1f, 0.7f, 2.0f));
+    rth_scene_set_ambient_light(c.s, v3(0.1f, 0.7f, 2.0f));                // :908: the bottom sky colour
     uint32_t g = add_diffuse(c, v3(1.0f, 0.0f, 0.0f), 1.0f, 0.0f, true, v3(1.0f, 1.0f, 0.0f));
     uint32_t glass = rth_add_translucent_material(c.s, v3(0), 1.8f, 0.0f);
     uint32_t metal = add_mat(c, 0, v3(0.95f), v3(0), 1.5f, 0.8f, 0.0f);
@@ -458,6 +461,8 @@ extern "C" int rth_take_picture(rth_scene* s, const rt_camera* camera, const rt_
     rt_scene* dev = nullptr;
     int err = rt_scene_upload(rth_scene_desc(s), device, &dev);
     if (err) return err;
+    const rt_v3 ambient = rth_scene_ambient_light(s);          // not in rt_scene_desc: passed on by hand
+    (void)rt_scene_set_ambient_light(dev, &ambient);
     rt_settings st = *settings;
     st.samples_per_pixel = spp;
     rt_tile_set tiles = {64, 64, 0, 1};

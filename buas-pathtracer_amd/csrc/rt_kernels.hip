@@ -2734,6 +2734,355 @@ __global__ void __launch_bounds__(DTB) k_drain(DevScene sc, rt_settings st, Fram
     }
 }
 
+// ----------------------------------------------------------------------
+// The recursive integrators (rt_scene_set_recursive_integrators): Whitted (raytrace_recursively,
+// RT/integrators.cpp:310-414) and Ground Truth Recursive (pathtrace_recursively, :428-471).
+//
+// Both fold the callee's result into the caller's pending terms on the way back up, and Whitted makes two
+// calls at a hit on a participating medium, so a sample is a tree walked depth-first: its float order
+// and its RandomSeries order are the recursion's.  k_recurse is k_drain's shape (persistent one-wave
+// blocks, a lane takes one camera sample and runs it to its end, idle lanes refill at call boundaries)
+// with an explicit frame stack in place of the C stack.
+//
+// A lane is always at a call: the ray (ro, rd), Whitted's previous_material, and `level`, the call's
+// depth (recursion = max_bounce_count - level).  One turn of the wave's loop runs that call for every
+// lane: intersect_scene when recursion > 0 (the prologue and the BVH walk, wave-cooperative as in
+// k_drain), Whitted's light loop (every light at every hit, one shadow ray each traced inline, the wave
+// stepping through the lights together), then either a value to return or a frame pushed and the next
+// call set up.  A lane with a value unwinds: it pops frames, folding the value into each, until a frame
+// wants another call (Whitted's reflected ray after the refracted subtree) or level 0 is left, where the
+// sample is splatted.  Nothing is traced while unwinding, so that loop is per lane.
+//
+// Frames: per thread of the persistent grid, level-major ([level][plane][thread], as the material stack),
+// RC_LEVELS levels (max_bounce_count <= 63: the deepest caller is at level 62) of RC_PLANES float4.  A
+// frame holds what the caller needs after the callee returns and nothing else:
+//   RF_PASS       Ground Truth Recursive's mirror call (:453): the value passes through
+//   RF_DIFFUSE    its hemisphere call (:463-466): a = brdf, s = max(0, dot(N, d))
+//   RF_REFRACTED  Whitted in a medium, awaiting the refracted subtree (:391): a = throughput, s = reflectance,
+//                 b / c = the reflected ray (its direction drew random_in_unit_sphere before the refracted
+//                 subtree ran, :386-392, so it is stored, never recomputed)
+//   RF_MEDIUM_REFLECTED  the same hit awaiting the reflected subtree (:392): b = refracted_light
+//   RF_REFLECTED  Whitted's reflectance > 0.05 branch (:402): a = diffuse_light, b = metallic_color, s = reflectance
+// previous_material is an argument of the call, read once at the callee's hit before any nested call: it
+// lives with the ray in registers, not in the frame.
+constexpr int RC_LEVELS = 64, RC_PLANES = 3;
+constexpr uint32_t RC_NO_MATERIAL = 0xFFFFFFFFu;    // previous_material = nullptr
+enum : uint32_t { RF_PASS = 0, RF_DIFFUSE = 1, RF_REFRACTED = 2, RF_MEDIUM_REFLECTED = 3, RF_REFLECTED = 4 };
+struct FrameStack {
+    float4* f;
+    uint32_t gtid, nthreads;
+    RT_D size_t at(uint32_t level, int plane) const { return ((size_t)level*RC_PLANES + plane)*nthreads + gtid; }
+    RT_D void put(uint32_t level, int plane, V3 v, float w) const { f[at(level, plane)] = make_float4(v.x, v.y, v.z, w); }
+    RT_D float4 get(uint32_t level, int plane) const { return f[at(level, plane)]; }
+};
+
+template <bool LST, int INTEG, bool REF = false>
+__global__ void __launch_bounds__(DTB) k_recurse(DevScene sc, rt_settings st, FrameParams fp, Pool pool, Counters* cnt,
+                                                 uint2* spill, float4* frames, V3 ambient) {
+    constexpr bool WHITTED = INTEG == RT_INTEGRATOR_WHITTED;
+    static_assert(WHITTED || INTEG == RT_INTEGRATOR_GROUND_TRUTH_RECURSIVE, "k_recurse: the two recursive integrators");
+    // this iteration's k_generate claimed G samples (its own arithmetic: k_bookkeep moves the cursor after us)
+    const unsigned long long remaining = remaining_samples(cnt);
+    const uint32_t gfree = cnt->gen_free;
+    const uint32_t G = remaining < (unsigned long long)gfree ? (uint32_t)remaining : gfree;
+    if (cnt->done || G == 0u) return;                                  // uniform
+    __shared__ uint2 lds_stack[STACK_LDS*DTB];
+    __shared__ float2 lds_bary[DTB];
+    Stack stk;
+    stk.lds = lds_stack; stk.spill = spill; stk.bary = lds_bary; stk.lane = threadIdx.x; stk.block = DTB;
+    stk.gtid = blockIdx.x*DTB + threadIdx.x; stk.nthreads = gridDim.x*DTB;
+    const FrameStack fs = {frames, stk.gtid, stk.nthreads};
+    const uint32_t lane = __lane_id();
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    // the pool's slots are handed out 64 at a time (k_bookkeep zeroes the head after every iteration);
+    // a slot holds a sample when k_generate left it S_NEW (its camera ray is counted) or S_DONE
+    // (max_bounce_count 0: no ray)
+    uint32_t* const head = &cnt->fetch[0][0][0];
+    uint32_t chunk_next = 0, chunk_end = 0;
+    bool exhausted = false, active = false, fresh = false;
+    uint32_t n_closest = 0, n_shadow = 0, n_traced = 0, n_traced_sh = 0, n_calls[2] = {0, 0};
+    // the lane's sample and its current call
+    V3 ro = {0, 0, 0}, rd = {0, 0, 0};
+    float vig = 0.0f;
+    uint32_t level = 0, prev_mat = RC_NO_MATERIAL, pixel = 0, key = 0, p = 0;
+    Rng rng = {0, 0, 0, 0};
+    StepCounts<LST> tally[2];                       // closest, shadow
+    for (;;) {
+        unsigned long long idle = __ballot(!active);
+        while (idle && !exhausted) {
+            if (chunk_next >= chunk_end) {
+                const int leader = __ffsll((long long)__ballot(true)) - 1;
+                uint32_t base = 0xFFFFFFFFu;
+                if (lane == (uint32_t)leader &&
+                    __hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < pool.n)
+                    base = atomicAdd(head, 64u);
+                base = __shfl(base, leader);
+                if (base >= pool.n) { exhausted = true; break; }
+                chunk_next = base;
+                chunk_end = min(base + 64u, pool.n);
+            }
+            const uint32_t avail = chunk_end - chunk_next;
+            const uint32_t rank = (uint32_t)__popcll(idle & lt_mask);
+            if (!active && rank < avail) {
+                const uint32_t slot = chunk_next + rank;
+                const uint8_t stv = pool.state[slot];
+                if (stv == S_NEW || stv == S_DONE) {
+                    const float4 o4 = ldnt(&pool.ray_o[slot]), d4 = ldnt(&pool.ray_d[slot]);
+                    const float2 pn2 = ldnt(&pool.prev_n[slot]);
+                    const uint4 r4 = ldnt(&pool.rng[slot]);
+                    pool.state[slot] = S_FREE;                  // taken: no other lane or launch runs it again
+                    ro = ld3(o4); rd = ld3(d4);
+                    vig = camera_vignette(fp, st, rd);
+                    p = __float_as_uint(pn2.y);
+                    pixel = __float_as_uint(o4.w); key = __float_as_uint(d4.w);
+                    rng = {r4.x, r4.y, r4.z, r4.w};
+                    level = 0; prev_mat = RC_NO_MATERIAL;
+                    active = true;
+                    fresh = stv == S_NEW;
+                }
+            }
+            chunk_next += min((uint32_t)__popcll(idle), avail);
+            idle = __ballot(!active);
+        }
+        if (__ballot(active) == 0ull) break;
+        const uint32_t canonical = fp.frame_count + (fp.list_xy && active ? fp.list_s[key] : key);
+        const SamplerState ss = {pixel & 0xFFFFu, pixel >> 16, canonical, st.sampling_strategy};
+        // intersect_scene (:315, :433) when recursion > 0
+        const bool query = active && level < st.max_bounce_count;
+        Prologue pro = {};
+        if (query) pro = ray_prologue(sc, ro, rd, FLT_MAX_, false, 0u);
+        // a fresh sample's camera ray is counted already (k_bookkeep from the claims, its queue entry, and
+        // k_generate its prologue's mesh instances)
+        n_closest += (query && !fresh) ? 1u : 0u;
+        n_traced += (query && !fresh && pro.bvh) ? 1u : 0u;
+        n_calls[0] += (query && !fresh) ? pro.calls : 0u;
+        fresh = false;
+        Hit h;
+        h.t = pro.t; h.code = pro.code; h.tri = 0; h.v = 0.0f; h.w = 0.0f;
+        {
+            Traversal<false, LST, STACK_LDS, REF> tr;
+            bool tracing = query && pro.bvh;
+            if (tracing) {
+                tr.init_rec(sc, stk, ro, rd, pro.inv_d, pro.t, 0u, pro.mlist);
+                tracing = tr.mode != TM_DONE;
+            }
+            for (int k = 1; __ballot(tracing); ++k) {
+                if (tracing && !tr.step(sc, stk)) tracing = false;
+                if (k % StepField<LST>::H == 0) tally[0].flush(tr.acc);   // one step per lane per k
+            }
+            tally[0].flush(tr.acc);
+            if (REF) tally[0].flush_ref(tr.rc);
+            if (query && pro.bvh && tr.code != RT_HIT_MISS) h = tr.result(stk);
+        }
+        bool ret = false, lit = false;
+        V3 val = {0, 0, 0};
+        // Whitted's hit, carried through the light loop
+        V3 I = {0, 0, 0}, N = {0, 0, 0};
+        float cos_i = 0.0f, hit_ior = 0.0f, hit_t = 0.0f;
+        uint32_t mat_id = 0;
+        bool inside = false;
+        if (active) {
+            if (!query) {                                               // recursion == 0: :413 / :470
+                if (!WHITTED) val = sample_sky(sc, rd);
+                ret = true;
+            } else if (h.code == RT_HIT_MISS) {                         // :410 / :470
+                val = sample_sky(sc, rd);
+                ret = true;
+            } else {
+                Ray ray; ray.o = ro; ray.d = rd;
+                uint32_t surf_id;
+                hit_geometry(sc, ray, h, I, N, surf_id);
+                const rt_material m = sc.materials[surf_id];
+                if (m.flags & RT_MATERIAL_EMISSIVE) {                   // :320-322 / :438-440: no throughput
+                    val = rv3(m.emission_color);
+                    ret = true;
+                } else if (WHITTED) {
+                    cos_i = -dot(rd, N);                                // :324-339
+                    inside = cos_i < 0.0f;
+                    mat_id = surf_id;
+                    hit_ior = m.ior;
+                    hit_t = h.t;
+                    if (inside) {
+                        N = neg(N);
+                        cos_i = -cos_i;
+                        if (prev_mat != RC_NO_MATERIAL) mat_id = prev_mat;
+                    }
+                    lit = true;
+                } else {
+                    float r0, r1, r2, r3;
+                    unilaterals(rng, r0, r1, r2, r3);                   // :442
+                    (void)r3;
+                    const float eta_i = 1.0f, eta_t = m.ior;
+                    const float eta = eta_i / eta_t;
+                    const float ci = -dot(rd, N);
+                    float cos_t;
+                    const float refl = fresnel_dielectric(ci, eta_i, eta_t, eta, cos_t);
+                    if (r0 < refl) {                                    // make_reflected_ray :267-270, :453
+                        const V3 nd = reflect(rd, N);
+                        fs.put(level, 0, v3s(0.0f), __uint_as_float(RF_PASS));
+                        ro = add(I, muls(nd, EPSILON)); rd = nd;
+                    } else {                                            // :456-463
+                        const V3 brdf = muls(evaluate_material(m, I), 1.0f / PI_32);
+                        const V3 R = map_to_hemisphere(N, V2{r1, r2});
+                        fs.put(level, 0, brdf, __uint_as_float(RF_DIFFUSE));
+                        fs.put(level, 1, v3s(0.0f), mx(0.0f, dot(N, R)));
+                        ro = add(I, muls(N, EPSILON)); rd = R;
+                    }
+                    ++level;
+                }
+            }
+        }
+        if (WHITTED) {
+            // the light loop (:347-371): every light, sample bounce index 0 at every depth, one shadow ray each
+            V3 ill = {0, 0, 0};
+            const uint32_t nlights = __ballot(lit) ? sc.light_count : 0u;
+            for (uint32_t li = 0; li < nlights; ++li) {                 // uniform
+                bool cast_shadow = false;
+                V3 sh_o = {0, 0, 0}, sh_d = {0, 0, 0}, sh_c = {0, 0, 0};
+                float sh_t = 0.0f;
+                uint32_t sh_light = 0;
+                if (lit) {
+                    const uint32_t lid = sc.lights[li];
+                    const rt_primitive light = sc.prims[lid];
+                    const V2 s2 = sample_2d(sc, ss, rng, S_DirectLighting, 0);
+                    // random_point_on_light (:199-228): another light type leaves the sample zero (N . L = 0)
+                    if (light.type == RT_PRIMITIVE_SPHERE) {
+                        const M34 lf = load_m34(&sc.fwd[light.transform_index]);
+                        const V3 towards = normalize(sub(translation(lf), I));
+                        const float rad = light.p[0];
+                        const V3 Nl = map_to_hemisphere(neg(towards), s2);
+                        const V3 pw = xform(lf, muls(Nl, rad), 1.0f);
+                        V3 Lv = sub(pw, I);
+                        const float dsq = length_sq(Lv);
+                        const float dist = __builtin_sqrtf(dsq);
+                        Lv = divs(Lv, dist);
+                        const float A = 2.0f*PI_32*rad*rad;
+                        const float ndl = dot(N, Lv);
+                        const float nndl = -dot(Nl, Lv);
+                        if (ndl > 0.0f && nndl > 0.0f) {
+                            sh_o = add(I, muls(Lv, EPSILON));
+                            sh_d = Lv;
+                            sh_t = dist - 2*EPSILON;
+                            sh_light = lid;
+                            sh_c = divs(smul(nndl*A*ndl, rv3(sc.materials[light.material_id].emission_color)), dsq);   // :365
+                            cast_shadow = true;
+                        }
+                    }
+                }
+                Prologue spro = {};
+                if (cast_shadow) spro = ray_prologue(sc, sh_o, sh_d, sh_t, true, sh_light);
+                n_calls[1] += cast_shadow ? spro.calls : 0u;
+                Traversal<true, LST, STACK_LDS, REF> tr;
+                bool tracing = cast_shadow && !spro.occluded && spro.bvh;
+                n_traced_sh += tracing ? 1u : 0u;
+                if (tracing) {
+                    tr.init_rec(sc, stk, sh_o, sh_d, spro.inv_d, sh_t, sh_light, spro.mlist);
+                    tracing = tr.mode != TM_DONE;
+                }
+                for (int k = 1; __ballot(tracing); ++k) {
+                    if (tracing && !tr.step(sc, stk)) tracing = false;
+                    if (k % StepField<LST>::H == 0) tally[1].flush(tr.acc);   // one step per lane per k
+                }
+                tally[1].flush(tr.acc);
+                if (REF) tally[1].flush_ref(tr.rc);
+                if (cast_shadow && !spro.occluded && (!spro.bvh || !tr.occluded)) ill = add(ill, sh_c);
+                n_shadow += cast_shadow ? 1u : 0u;
+            }
+            if (lit) {
+                const rt_material m = sc.materials[mat_id];             // previous_material's when hit from inside
+                float eta_i = 1.0f, eta_t = hit_ior;                    // the hit material's ior (:327-335)
+                if (inside) { eta_i = hit_ior; eta_t = 1.0f; }
+                V3 thr = v3s(1.0f);
+                if (inside && m.is_participating_medium) {              // :341-345
+                    thr.x *= d_expf(-m.absorb.x*hit_t);
+                    thr.y *= d_expf(-m.absorb.y*hit_t);
+                    thr.z *= d_expf(-m.absorb.z*hit_t);
+                }
+                ill = muls(ill, 1.0f / (float)1);                       // light_sample_count (:370)
+                ill = add(ill, ambient);                                // :371
+                const V3 brdf = smul(1.0f / PI_32, evaluate_material(m, I));
+                const V3 metallic_color = lerp3(v3s(1.0f), rv3(m.albedo), m.metallic);
+                const float eta = eta_i / eta_t;
+                float cos_t;
+                float refl = fresnel_dielectric(cos_i, eta_i, eta_t, eta, cos_t);
+                refl = lerpf_(refl, 1.0f, m.metallic);
+                const bool medium = m.is_participating_medium != 0;
+                if (medium || refl > 0.05f) {
+                    // refracted_d as written, total internal reflection or not (:384)
+                    const V3 fd = add(smul(eta, rd), muls(N, (eta*cos_i - cos_t)));
+                    V3 nd = reflect(rd, N);                             // :386-389 / :396-399
+                    if (m.roughness > 0.0f)
+                        nd = normalize(add(smul(1.0f + EPSILON, nd), smul(m.roughness, random_in_unit_sphere(rng))));
+                    const V3 no = add(I, muls(nd, EPSILON));
+                    if (medium) {                                       // :391: the refracted call first
+                        fs.put(level, 0, thr, __uint_as_float(RF_REFRACTED));
+                        fs.put(level, 1, no, refl);
+                        fs.put(level, 2, nd, 0.0f);
+                        ro = add(I, muls(fd, EPSILON)); rd = fd; prev_mat = mat_id;
+                    } else {                                            // :401-402
+                        fs.put(level, 0, mul(mul(thr, brdf), ill), __uint_as_float(RF_REFLECTED));
+                        fs.put(level, 1, metallic_color, refl);
+                        ro = no; rd = nd; prev_mat = RC_NO_MATERIAL;
+                    }
+                    ++level;
+                } else {
+                    val = mul(mul(thr, brdf), ill);                     // :406
+                    ret = true;
+                }
+            }
+        }
+        if (active && ret) {
+            while (ret && level > 0u) {
+                --level;                                                // the caller's frame
+                const float4 f0 = fs.get(level, 0);
+                const uint32_t kind = __float_as_uint(f0.w);
+                if (kind == RF_DIFFUSE) {                               // :464-466
+                    const float c = fs.get(level, 1).w;
+                    val = muls(val, c);
+                    val = mul(smul(2.0f*PI_32, val), ld3(f0));
+                } else if (kind == RF_REFRACTED) {                      // :391 returned: :392
+                    const float4 f1 = fs.get(level, 1), f2 = fs.get(level, 2);
+                    fs.put(level, 0, ld3(f0), __uint_as_float(RF_MEDIUM_REFLECTED));
+                    fs.put(level, 1, val, f1.w);
+                    ro = ld3(f1); rd = ld3(f2); prev_mat = RC_NO_MATERIAL;
+                    ++level;
+                    ret = false;
+                } else if (kind == RF_MEDIUM_REFLECTED) {               // :394
+                    const float4 f1 = fs.get(level, 1);
+                    val = lerp3(mul(ld3(f0), ld3(f1)), val, f1.w);
+                } else if (kind == RF_REFLECTED) {                      // :402-404
+                    const float4 f1 = fs.get(level, 1);
+                    val = lerp3(ld3(f0), mul(ld3(f1), val), f1.w);
+                }                                                       // RF_PASS: :453
+            }
+            if (ret) {
+                const uint32_t s = fp.list_xy ? fp.list_s[key] : key;
+                const V2 j = sample_jitter(sc, st, fp, pixel & 0xFFFFu, pixel >> 16, s);
+                splat_sample(fp, pool, val, vig, make_float2(j.x, j.y), key, p);
+                active = false;
+            }
+        }
+    }
+    unsigned long long c[4] = {n_closest, n_shadow, n_traced, n_traced_sh};
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        for (int m = 32; m; m >>= 1) c[k] += __shfl_xor(c[k], m);
+    if (lane == 0) {
+        if (c[0]) atomicAdd(&cnt->closest_rays, c[0]);
+        if (c[1]) atomicAdd(&cnt->shadow_rays, c[1]);
+        if (c[2]) atomicAdd(&cnt->traced_rays[0], c[2]);
+        if (c[3]) atomicAdd(&cnt->traced_rays[1], c[3]);
+    }
+    unsigned long long* trav = cnt->trav[blockIdx.x % NSHARD];
+    tally[0].commit(trav, 0, true);
+    tally[1].commit(trav, 1, true);
+    const uint32_t calls0 = __ockl_wfred_add_u32(n_calls[0]), calls1 = __ockl_wfred_add_u32(n_calls[1]);
+    if (lane == 0) {
+        if (calls0) atomicAdd(&trav[TV_CALLS], (unsigned long long)calls0);
+        if (calls1) atomicAdd(&trav[TV_N + TV_CALLS], (unsigned long long)calls1);
+    }
+}
+
 // k_resolve — splat_filter as a gather (RT/raytracer.cpp:187-259, :476-488).
 // Every output pixel sums its neighbours' samples in exactly the order the
 // reference's single-threaded renderer splats them: tiles in descending index
@@ -3374,6 +3723,12 @@ struct rt_scene {
     uint32_t bvh_depth = 0;
     uint32_t bvh_depth_ref = 0;         // stack entries a reference-unit walk (with markers) may hold
     rt_scene_config cfg = {};           // rt_scene_set_config; read at every frame, never the environment
+    // rt_scene_set_recursive_integrators: Whitted and Ground Truth Recursive (k_recurse).  The frame stack
+    // is [RC_LEVELS][RC_PLANES][recurse_grid*DTB] float4, held while the opt-in is on.
+    bool recursive = false;
+    float4* frames = nullptr;
+    uint32_t recurse_grid = 0;          // persistent k_recurse blocks (<= trace_grid*TB/DTB: the spill area)
+    V3 ambient = {0, 0, 0};             // Scene::ambient_light (RT/scene.h:102), read by Whitted only
 };
 
 namespace {
@@ -3628,6 +3983,8 @@ inline bool integrator_on_device(int i) {
            i == RT_INTEGRATOR_DISTANCES;
 }
 inline bool integrator_first_hit(int i) { return i == RT_INTEGRATOR_NORMALS || i == RT_INTEGRATOR_DISTANCES; }
+// the two a scene opts into (rt_scene_set_recursive_integrators): k_recurse and its frame stack
+inline bool integrator_recursive(int i) { return i == RT_INTEGRATOR_WHITTED || i == RT_INTEGRATOR_GROUND_TRUTH_RECURSIVE; }
 
 // The settings the kernels and the schedule see.  Normals and Distances never read max_bounce_count
 // (RT/integrators.cpp:544-579): they trace their camera ray even when it is 0, and their path ends at that
@@ -3639,10 +3996,10 @@ rt_settings device_settings(const rt_settings& st) {
     return e;
 }
 
-int check_inputs(const rt_settings* st, const rt_filter_cache* f) {
+int check_inputs(const rt_scene* s, const rt_settings* st, const rt_filter_cache* f) {
     if (!st || !f) { set_error("null settings/filter"); return RT_ERROR_INVALID; }
     if (st->integrator < 0 || st->integrator >= RT_INTEGRATOR_COUNT) { set_error("bad integrator"); return RT_ERROR_INVALID; }
-    if (!integrator_on_device(st->integrator)) {
+    if (!integrator_on_device(st->integrator) && !(s && s->recursive && integrator_recursive(st->integrator))) {
         // Whitted branches in a medium and both fold their results on the way back up the recursion
         // (RT/integrators.cpp:391-392, :417-426, :474-483): not reproducible by a forward wavefront
         set_error(std::string("the ") + INTEGRATOR_NAMES[st->integrator] +
@@ -3674,9 +4031,10 @@ inline bool debug_timing() { static const bool on = getenv("RT_DEBUG_TIMING") !=
 // full frame gains from 8M paths (6.3M 239.3 / 239.4, 8.4M 236.7 / 237.6, 10.5M 237.7 / 238.8, 12.6M
 // 239.8 / 240.3 ms): the upper bound is 4 x 2^21 (rank 0 of 2 at 8.4M: 128.7 -> 128.8 / 129.2, unchanged).
 struct FrameShape { int nparts; uint32_t pool_n; };
-FrameShape frame_shape(const rt_scene* s, unsigned long long total, uint32_t passes) {
+FrameShape frame_shape(const rt_scene* s, int integrator, unsigned long long total, uint32_t passes) {
     FrameShape f;
     f.nparts = s->cfg.partitions > 0 ? std::min(MAX_PARTITIONS, (int)s->cfg.partitions) : 4;
+    if (integrator_recursive(integrator)) f.nparts = 1;        // one frame stack: k_recurse's grid fills the GPU alone
     if (passes) f.nparts = std::max(1, std::min<int>(f.nparts, (int)passes));   // partitions own whole passes
     uint32_t pool_n = s->cfg.path_pool > 0 ? (uint32_t)s->cfg.path_pool : g_pool_override;
     if (!pool_n) {
@@ -3734,7 +4092,8 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
     const int integ = st->integrator;
     const bool advanced = integ == RT_INTEGRATOR_ADVANCED;
     const bool listed = fp.list_xy != nullptr;
-    const FrameShape shape = frame_shape(s, total, listed ? 0u : sp.passes);
+    const bool recursive = integrator_recursive(integ);        // k_recurse: see the schedule in iterate()
+    const FrameShape shape = frame_shape(s, integ, total, listed ? 0u : sp.passes);
     const int nparts = shape.nparts;
     const uint32_t pool_n = shape.pool_n;
     // k_bookkeep's workgroup size by the pool (BK_LARGE_POOL, see k_bookkeep)
@@ -3757,7 +4116,8 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
     Run run[MAX_PARTITIONS] = {};
     double kms[RT_KERNEL_COUNT] = {};
     uint64_t klaunch[RT_KERNEL_COUNT] = {};
-    const uint32_t life = std::max<uint32_t>(st->max_bounce_count, 1u);
+    // (a recursive integrator's sample is splatted by the k_recurse of the iteration that claimed it)
+    const uint32_t life = recursive ? 1u : std::max<uint32_t>(st->max_bounce_count, 1u);
     // live paths at which the drain is fused (k_drain): 2.5 times its grid's lanes, or a tenth of the
     // pool if more (r02 sweeps: rank 0 of 8, 3.3M-path pools: 1x the lanes 40.5 ms, 2.5x 39.3, 4.5x 40.0,
     // 9x 41.0; the full frame's 8.4M-path pools: 2.5x 235.8, 600k 234.1-235.2, 1M 234.2-234.3 ms);
@@ -3862,7 +4222,8 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
             const int slot = (int)((r.chunk_first[b] + i) % EV_SLOTS);
             for (int kern = 0; kern < RT_KERNEL_COUNT; ++kern) {
                 // (the splat runs inside k_generate; merged, the shadow rays inside k_trace: no events of their own)
-                if (!((prof >> kern) & 1u) || kern == RT_KERNEL_SPLAT || (!connect && kern == RT_KERNEL_CONNECT)) continue;
+                if (!((prof >> kern) & 1u) || kern == RT_KERNEL_SPLAT || (!connect && kern == RT_KERNEL_CONNECT) ||
+                    (recursive && kern == RT_KERNEL_EXTEND)) continue;
                 if (kern == RT_KERNEL_RESOLVE && !r.res_ev[slot]) continue;
                 float ms = 0.0f;
                 if (hipEventElapsedTime(&ms, ev(k, slot, kern, 0), ev(k, slot, kern, 1)) == hipSuccess) {
@@ -3901,7 +4262,37 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
         const int fuse = (r.near && fuse_paths && r.iters % every == every - 1) ? 1 : 0;
         b(RT_KERNEL_GENERATE);
         k_generate<<<r.grid, BLOCK, 0, q>>>(ds, *st, fp, pg, pt.cnt, r.cur);
-        e(RT_KERNEL_GENERATE); b(RT_KERNEL_EXTEND);
+        e(RT_KERNEL_GENERATE);
+        if (recursive) {
+            // Whitted / Ground Truth Recursive: generate -> k_recurse -> bookkeep.  No path outlives its
+            // iteration: k_recurse runs every sample k_generate claimed to its end and splats it, so no wave
+            // keeps a survivor, every slot is free again (free_w stays 64, the finished arrays stay empty)
+            // and the extension queue k_generate filled is only counted (k_bookkeep: the camera rays that
+            // enter a BVH).  Timed as the shade stage.
+            b(RT_KERNEL_SHADE);
+            auto recurse = [&](auto tag) {
+                constexpr int INTEG = decltype(tag)::value;
+                const uint32_t g = s->recurse_grid;
+                if (ds.listed_only) k_recurse<true, INTEG><<<g, DTB, 0, q>>>(ds, *st, fp, pv, pt.cnt, pt.spill, s->frames, s->ambient);
+                else if (ref) k_recurse<false, INTEG, true><<<g, DTB, 0, q>>>(ds, *st, fp, pv, pt.cnt, pt.spill, s->frames, s->ambient);
+                else k_recurse<false, INTEG><<<g, DTB, 0, q>>>(ds, *st, fp, pv, pt.cnt, pt.spill, s->frames, s->ambient);
+            };
+            if (integ == RT_INTEGRATOR_WHITTED) recurse(std::integral_constant<int, RT_INTEGRATOR_WHITTED>{});
+            else recurse(std::integral_constant<int, RT_INTEGRATOR_GROUND_TRUTH_RECURSIVE>{});
+            e(RT_KERNEL_SHADE);
+            const bool res = stream_splat && (plan || r.drain);
+            launch_bookkeep(pt.cnt, pv, r.grid, r.cur, BK_ITER, plan_of(k, res ? 1u : 0u), q);
+            r.res_ev[slot] = res && ((prof >> RT_KERNEL_RESOLVE) & 1u);
+            if (res) {
+                b(RT_KERNEL_RESOLVE);
+                launch_resolve_tiles(sp, fp, pv, pt.cnt, r.dst, q);
+                e(RT_KERNEL_RESOLVE);
+            }
+            ++r.iters;
+            r.cur ^= 1;
+            return;
+        }
+        b(RT_KERNEL_EXTEND);
         // the trace launch: this iteration's extension rays (merged: then the previous k_shade's shadow rays)
         auto trace = [&](auto ph, const Pool& tp, int tcur, uint32_t grid) {
             constexpr int PH = decltype(ph)::value;
@@ -4341,6 +4732,55 @@ int rt_find_integrator(const char* name) {          // find_integrator (RT/integ
     return RT_INTEGRATOR_ADVANCED;
 }
 int rt_integrator_supported(int integrator) { return integrator_on_device(integrator) ? 1 : 0; }
+
+int rt_scene_integrator_supported(const rt_scene* s, int integrator) {
+    return (integrator_on_device(integrator) || (s && s->recursive && integrator_recursive(integrator))) ? 1 : 0;
+}
+
+int rt_scene_set_ambient_light(rt_scene* s, const rt_v3* a) {
+    if (!s || !a) { set_error("null argument"); return RT_ERROR_INVALID; }
+    s->ambient = rv3(*a);
+    return RT_OK;
+}
+
+int rt_scene_set_recursive_integrators(rt_scene* s, int enable) {
+    if (!s) { set_error("null argument"); return RT_ERROR_INVALID; }
+    if (!enable) {
+        if (s->frames) { HIP_OK(hipSetDevice(s->device)); (void)hipFree(s->frames); }
+        s->frames = nullptr;
+        s->recursive = false;
+        return RT_OK;
+    }
+    if (s->recursive) return RT_OK;
+    HIP_OK(hipSetDevice(s->device));
+    // k_recurse's grid: the one-wave blocks that fit at once (the largest instantiation decides), no more
+    // lanes than the traversal spill area is sized for
+    hipDeviceProp_t prop;
+    HIP_OK(hipGetDeviceProperties(&prop, s->device));
+    int per_cu = 0;
+    auto fit = [&](auto kernel) {
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, DTB, 0) != hipSuccess || n < 1) n = 1;
+        per_cu = per_cu ? std::min(per_cu, n) : n;
+    };
+    fit(k_recurse<true, RT_INTEGRATOR_WHITTED>);
+    fit(k_recurse<false, RT_INTEGRATOR_WHITTED>);
+    fit(k_recurse<false, RT_INTEGRATOR_WHITTED, true>);
+    fit(k_recurse<true, RT_INTEGRATOR_GROUND_TRUTH_RECURSIVE>);
+    fit(k_recurse<false, RT_INTEGRATOR_GROUND_TRUTH_RECURSIVE>);
+    fit(k_recurse<false, RT_INTEGRATOR_GROUND_TRUTH_RECURSIVE, true>);
+    const uint32_t grid = std::max(1u, std::min(s->trace_grid*(uint32_t)(TB / DTB), (uint32_t)(prop.multiProcessorCount*per_cu)));
+    const size_t bytes = sizeof(float4)*(size_t)RC_LEVELS*RC_PLANES*grid*DTB;
+    if (hipMalloc(&s->frames, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        s->frames = nullptr;
+        set_error("rt_scene_set_recursive_integrators: no memory for the frame stack");
+        return RT_ERROR_OUT_OF_MEMORY;
+    }
+    s->recurse_grid = grid;
+    s->recursive = true;
+    return RT_OK;
+}
 const char* rt_last_error(void) { return g_error.c_str(); }
 
 int rt_device_count(int* out) {
@@ -4720,6 +5160,7 @@ int rt_scene_free(rt_scene* s) {
     if (s->d_lut) (void)hipFree(s->d_lut);
     if (s->d_partials) (void)hipFree(s->d_partials);
     if (s->d_aux) (void)hipFree(s->d_aux);
+    if (s->frames) (void)hipFree(s->frames);
     delete s;
     return RT_OK;
 }
@@ -4776,7 +5217,7 @@ int rt_render_device(rt_scene* s, const rt_camera* camera, const rt_settings* st
                      uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
                      float* d_pixels, void* hip_stream, rt_stats* stats) {
     if (!s || !camera || !tiles || !d_pixels || !w || !h) { set_error("null argument"); return RT_ERROR_INVALID; }
-    int err = check_inputs(st, filter);
+    int err = check_inputs(s, st, filter);
     if (err) return err;
     const rt_settings dev_st = device_settings(*st);
     st = &dev_st;
@@ -4880,7 +5321,7 @@ int rt_render_device(rt_scene* s, const rt_camera* camera, const rt_settings* st
     // one pass per partition does not fit.
     const uint32_t spp = pass_hi - pass_lo;                       // this shard's passes
     const int ks = fp.cache_size ? fp.kernel_size : 0;
-    const FrameShape shape = frame_shape(s, total, spp);
+    const FrameShape shape = frame_shape(s, st->integrator, total, spp);
     int want_mode = s->cfg.splat_mode >= 0 ? s->cfg.splat_mode : g_splat_mode;
     // k_resolve gathers passes 0..spp-1 of one record array: a pass shard never takes the exact splat
     if (by_pass && want_mode == RT_SPLAT_EXACT) want_mode = RT_SPLAT_STREAM;
@@ -5111,7 +5552,7 @@ int rt_trace_samples(rt_scene* s, const rt_camera* camera, const rt_settings* st
                      uint32_t count, const uint32_t* pixel_xy, const uint32_t* sample_offset,
                      float* out, rt_stats* stats) {
     rt_filter_cache box = {};
-    int err = check_inputs(st, &box);
+    int err = check_inputs(s, st, &box);
     if (err) return err;
     const rt_settings dev_st = device_settings(*st);
     st = &dev_st;

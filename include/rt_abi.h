@@ -138,8 +138,8 @@ enum rt_sampling_strategy {                                    /* RT/samplers.h:
 
 enum rt_integrator {                                           /* g_integrators RT/integrators.cpp:823-830, by table index */
     RT_INTEGRATOR_ADVANCED               = 0,   /* "Advanced Pathtracer" (:581-821): NEE, MIS, roulette, media */
-    RT_INTEGRATOR_WHITTED                = 1,   /* "Whitted" (:417-426): not on the device (see below)          */
-    RT_INTEGRATOR_GROUND_TRUTH_RECURSIVE = 2,   /* "Ground Truth Recursive" (:474-483): not on the device       */
+    RT_INTEGRATOR_WHITTED                = 1,   /* "Whitted" (:310-426): a per-scene opt-in (see below)         */
+    RT_INTEGRATOR_GROUND_TRUTH_RECURSIVE = 2,   /* "Ground Truth Recursive" (:428-483): a per-scene opt-in      */
     RT_INTEGRATOR_GROUND_TRUTH_ITERATIVE = 3,   /* "Ground Truth Iterative" (:486-541): brute-force path tracer */
     RT_INTEGRATOR_NORMALS                = 4,   /* "Normals" (:544-560): first hit, 0.5*(1 + N)                 */
     RT_INTEGRATOR_DISTANCES              = 5,   /* "Distances" (:563-579): first hit, 1 - saturate(t/15)        */
@@ -147,7 +147,8 @@ enum rt_integrator {                                           /* g_integrators 
 };
 /* The render entries take 0, 3, 4 and 5.  Whitted and Ground Truth Recursive fold their results on the way
  * back up a recursion (Whitted also branches in a medium), which a forward wavefront cannot reproduce without
- * a per-path recursion stack: they return RT_ERROR_INVALID by name.  Ground Truth Iterative, Normals and
+ * a per-path recursion stack: they return RT_ERROR_INVALID by name, unless the scene has opted in with
+ * rt_scene_set_recursive_integrators (below), which allocates that stack.  Ground Truth Iterative, Normals and
  * Distances cast no shadow rays (rt_stats::shadow_rays == 0) and ignore rt_set_env_sampling; Normals and
  * Distances trace their one camera ray whatever max_bounce_count says, as the reference's do. */
 
@@ -311,6 +312,21 @@ int         rt_device_count(int* out_count);
 const char* rt_integrator_name(int integrator);
 int         rt_find_integrator(const char* name);
 int         rt_integrator_supported(int integrator);
+
+/* Whitted and Ground Truth Recursive as a per-scene opt-in.  rt_scene_set_recursive_integrators(scene, 1):
+ * rt_render, rt_render_device, rt_render_picture and rt_trace_samples take integrators 1 and 2 for this
+ * scene; it allocates a frame stack on the scene's device (64 levels of 48 bytes per lane of a persistent
+ * kernel that fills the GPU: 384 MiB on an MI355X), which (scene, 0) or rt_scene_free releases.  Off
+ * (the default) they return RT_ERROR_INVALID as before.  Their frames run as one partition, a camera sample
+ * per lane walked depth-first; Whitted makes two calls at every hit on a participating medium, so its cost
+ * doubles per medium bounce: keep max_bounce_count small where a medium is visible.
+ * rt_scene_integrator_supported: rt_integrator_supported plus 1 and 2 when the scene has the opt-in on; with
+ * a NULL scene it equals rt_integrator_supported.
+ * rt_scene_set_ambient_light: Scene::ambient_light (RT/scene.h:102), which only Whitted reads
+ * (RT/integrators.cpp:371); rt_scene_desc has no such field.  Default (0, 0, 0). */
+int rt_scene_set_recursive_integrators(rt_scene* scene, int enable);
+int rt_scene_integrator_supported(const rt_scene* scene, int integrator);
+int rt_scene_set_ambient_light(rt_scene* scene, const rt_v3* ambient_light);
 
 /* Upload a flattened scene to `device` (create_scene_bvh must have run on
  * the host: RT/scene.cpp:173-242).  The device copy is owned by *out. */

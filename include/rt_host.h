@@ -84,6 +84,10 @@ int      rth_mesh_bvh_info(rth_scene* s, uint32_t mesh_id, rth_bvh_info* out);
 int      rth_scene_bvh_info(rth_scene* s, rth_bvh_info* out);
 
 void     rth_set_sky(rth_scene* s, rt_v3 top, rt_v3 bot);
+/* Scene::ambient_light (RT/scene.h:102): added to the Whitted integrator's illumination, read by nothing
+ * else.  Not part of rt_scene_desc: the host passes it on with rt_scene_set_ambient_light after the upload. */
+void     rth_scene_set_ambient_light(rth_scene* s, rt_v3 ambient_light);
+rt_v3    rth_scene_ambient_light(const rth_scene* s);
 /* load_environment_map: parse_hdr + luma CDF (the CDF is built, as in the reference) */
 int      rth_load_environment_map(rth_scene* s, const char* hdr_path);
 /* The same from pixels in memory (w*h, row 0 = the bottom row sample_sky reads at v = 0) */
