@@ -324,6 +324,13 @@ class DeviceScene:
         _check(lib().rt_scene_get_config(self._h, C.byref(c)))
         return c
 
+    def ramp_stats(self):
+        """rt_scene_ramp_stats: (shade iterations after the last claim and before the fused drain, paths
+        they shaded) of the last frame, summed over its partitions."""
+        it, paths = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().rt_scene_ramp_stats(self._h, C.byref(it), C.byref(paths)))
+        return int(it.value), int(paths.value)
+
     def configure(self, **fields):
         """rt_scene_set_config with the named fields changed, e.g. configure(partitions=1,
         splat_mode=abi.RT_SPLAT_EXACT).  Returns the previous configuration (pass it to

@@ -182,7 +182,8 @@ class SceneConfig(C.Structure):       # rt_scene_config (per-scene schedule and 
                 ("splat_chunk", C.c_int32), ("splat_ring", C.c_int32), ("sample_budget_gb", C.c_double),
                 ("resolve_tall_pixels", C.c_int64), ("debug_traversal", C.c_int32), ("traversal_ref", C.c_int32),
                 ("drain_every", C.c_int32), ("shadow_launch", C.c_int32),  # ABI 8
-                ("reserved", C.c_int32 * 4)]
+                ("ramp_shade", C.c_int32),      # 0 auto (on), 1 on, 2 off: the dense ramp-down shade
+                ("reserved", C.c_int32 * 3)]
 
 
 class BvhInfo(C.Structure):
@@ -218,6 +219,8 @@ ABI_FUNCTIONS = {
     "rt_debug_top_sequences": (C.c_int, [P(BvhNode), C.c_uint32, C.c_uint32, P(C.c_float), C.c_uint32,
                                          P(C.c_uint32)]),
     "rt_debug_claim_slots": (C.c_int, [P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32)]),
+    "rt_debug_rank_slots": (C.c_int, [P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32)]),
+    "rt_scene_ramp_stats": (C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64)]),
     "rt_debug_verify_rcp": (C.c_int, [C.c_int, P(C.c_uint64), P(C.c_uint32)]),
     "rt_set_profiling": (C.c_int, [C.c_int]),
     "rt_set_profiling_stages": (C.c_int, [C.c_uint32]),

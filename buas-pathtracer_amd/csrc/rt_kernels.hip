@@ -1289,7 +1289,12 @@ struct Pool {
     uint2*    fin2_k;
     uint32_t* fin2_px;
     uint32_t* fin2_w;
+    // free_w is double-buffered with the path buffers as well (r09): k_shade writes its parity's counts
+    // (k_bookkeep scans them), and the next iteration sees them as free_p, the previous k_shade's: the
+    // counts k_generate's claims follow, and the ones the dense ramp k_shade finds its paths by while its
+    // blocks, in no order, write their new counts to free_w.
     uint32_t* free_w;
+    uint32_t* free_p;
     // This partition's sample records (the deterministic splats): pass s, tile-list pixel p at
     // ((s - rec_pass0) % rec_ring)*P + p.  A ring of rec_ring passes in the streaming splat
     // (k_resolve_tiles frees passes while the frame renders), the partition's whole pass range
@@ -1353,6 +1358,13 @@ struct Counters {
     uint32_t res_cursor;                 // passes below it are resolved (or planned for the next resolve)
     uint32_t res_from, res_to;           // the pass range the next k_resolve_tiles resolves (empty: none)
     unsigned long long hist[128];        // next_sample after the bookkeep of iteration i, at [i % 128]
+    // The ramp-down (k_bookkeep): every sample is claimed, paths are alive and the drain is not fused, so
+    // the next k_shade finds pool.n - gen_free paths at the fronts of the waves and nothing else.  `ramp`
+    // is that state for the next iteration (the dense ramp k_shade keys on it); ramp_iters / ramp_paths
+    // count those iterations and the paths they shade over the frame (rt_scene_ramp_stats).
+    uint32_t ramp;
+    uint32_t ramp_iters;
+    unsigned long long ramp_paths;
 };
 
 struct FrameParams {
@@ -1698,19 +1710,41 @@ __host__ __device__ inline void claim_narrow(uint32_t& lo, uint32_t& n, uint32_t
 // (three dependent loads for C3's 8192 blocks; k_bookkeep, one workgroup on every partition's critical
 // chain, is left as it is), then the lanes find their own blocks among the next 64 bases with wave
 // shuffles, and again if the 64 claims span more blocks than that (blocks with next to nothing free).
-RT_D uint32_t claim_to_slot(const Pool& pool, uint32_t nblocks, uint32_t c0, uint32_t lane, bool act) {
+//
+// The ramp-down's rank -> slot map (r09, the dense ramp k_shade) is the mirror: the alive paths are the
+// waves' fronts, ranked in slot order, block b holds the ranks from 256 b - claim_base[b] on (its first
+// rank: the paths alive in the blocks before it), and those keys ascend like the first claims, so the same
+// search finds a rank's block (RANK).  Blocks with equal keys hold nothing but the last one (an empty
+// block repeats its neighbour's key; a full block repeats its neighbour's first claim): the search takes
+// the last block whose key is <= the number, for claims and ranks alike.
+__host__ __device__ inline uint32_t rank_key(uint32_t b, uint32_t claim_base) { return b*(uint32_t)BLOCK - claim_base; }
+// The slot of a block's r-th alive path (r < 256 - f0 - f1 - f2 - f3): each wave's survivors are its first slots.
+__host__ __device__ inline uint32_t rank_slot(uint32_t b, uint32_t r, uint32_t f0, uint32_t f1, uint32_t f2) {
+    uint32_t w = 0, a = 64u - f0;
+    if (r >= a) { r -= a; w = 1; a = 64u - f1; }
+    if (w == 1 && r >= a) { r -= a; w = 2; a = 64u - f2; }
+    if (w == 2 && r >= a) { r -= a; w = 3; }
+    return b*(uint32_t)BLOCK + w*64u + r;
+}
+template <bool RANK>
+RT_D uint32_t block_key(const Pool& pool, uint32_t b) {
+    const uint32_t v = pool.claim_base[b];
+    return RANK ? rank_key(b, v) : v;
+}
+template <bool RANK>
+RT_D uint32_t find_block(const Pool& pool, uint32_t nblocks, uint32_t c0, uint32_t lane, bool act) {
     uint32_t lo = 0, n = nblocks;
     while (n > 64u) {                                                   // uniform
         const uint32_t idx = lo + lane*claim_stride(n);
-        const uint32_t v = idx < lo + n ? pool.claim_base[idx] : 0xFFFFFFFFu;
+        const uint32_t v = idx < lo + n ? block_key<RANK>(pool, idx) : 0xFFFFFFFFu;
         claim_narrow(lo, n, (uint32_t)__popcll(__ballot(v <= c0)));
     }
     const uint32_t c = c0 + lane;
     uint32_t b = 0;
     bool found = !act;
-    for (uint32_t at = lo;; at += 64u) {                                // uniform; claim_base[at] <= c for the lanes left
+    for (uint32_t at = lo;; at += 64u) {                                // uniform; key[at] <= c for the lanes left
         const uint32_t idx = at + 1u + lane;
-        const uint32_t nb = idx < nblocks ? pool.claim_base[idx] : 0xFFFFFFFFu;   // the next blocks' first claims
+        const uint32_t nb = idx < nblocks ? block_key<RANK>(pool, idx) : 0xFFFFFFFFu;   // the next blocks' keys
         uint32_t pos = 0;                                               // how many of them are <= c (they ascend)
 #pragma unroll
         for (uint32_t step = 32u; step; step >>= 1)
@@ -1720,8 +1754,18 @@ RT_D uint32_t claim_to_slot(const Pool& pool, uint32_t nblocks, uint32_t c0, uin
         if (!__ballot(!found)) break;
     }
     if (b >= nblocks) b = nblocks - 1u;                                 // (counts that disagree with the scan: stay inside)
-    const uint4 f = reinterpret_cast<const uint4*>(pool.free_w)[b];
-    return claim_slot(b, c - pool.claim_base[b], f.x, f.y, f.z, f.w);
+    return b;
+}
+RT_D uint32_t claim_to_slot(const Pool& pool, uint32_t nblocks, uint32_t c0, uint32_t lane, bool act) {
+    const uint32_t b = find_block<false>(pool, nblocks, c0, lane, act);
+    const uint4 f = reinterpret_cast<const uint4*>(pool.free_p)[b];
+    return claim_slot(b, c0 + lane - pool.claim_base[b], f.x, f.y, f.z, f.w);
+}
+// The slots of the alive paths of ranks r0 + lane (as claim_to_slot: r0 wave-uniform, every lane calls it)
+RT_D uint32_t rank_to_slot(const Pool& pool, uint32_t nblocks, uint32_t r0, uint32_t lane, bool act) {
+    const uint32_t b = find_block<true>(pool, nblocks, r0, lane, act);
+    const uint4 f = reinterpret_cast<const uint4*>(pool.free_p)[b];
+    return rank_slot(b, r0 + lane - block_key<true>(pool, b), f.x, f.y, f.z);
 }
 
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(80))) k_generate(DevScene sc_g, rt_settings st, FrameParams fp, Pool pool,
@@ -1787,9 +1831,9 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(80))) k_
     // the retired pool after k_drain_list) go idle.  Slot-ordered, with the claim numbers of the
     // slot-ordered form; skipped, wave-uniformly, in the iterations that fill every free slot.
     if (G < gfree) {
-        const uint32_t first = 64u - pool.free_w[wbase];
+        const uint32_t first = 64u - pool.free_p[wbase];
         uint32_t before = 0;
-        for (uint32_t w = 0; w < wave; ++w) before += pool.free_w[wbase - wave + w];
+        for (uint32_t w = 0; w < wave; ++w) before += pool.free_p[wbase - wave + w];
         const uint32_t claim = pool.claim_base[blockIdx.x] + before + (lane - first);
         if (lane >= first && (G == 0u || claim >= G)) pool.state[own] = S_FREE;
     }
@@ -2033,7 +2077,7 @@ __global__ void __launch_bounds__(TB) RT_TRACE_ATTR k_trace(DevScene sc, Pool po
 #ifndef RT_SHADE_WAVES
 #define RT_SHADE_WAVES 8            // tuning builds: -DRT_SHADE_WAVES=7
 #endif
-#define RT_SHADE_ATTR __attribute__((amdgpu_waves_per_eu((IN_LDS && !ENV) ? RT_SHADE_WAVES : 7)))
+#define RT_SHADE_ATTR __attribute__((amdgpu_waves_per_eu((IN_LDS && !ENV && !RAMP) ? RT_SHADE_WAVES : 7)))
 // One bounce of advanced_integrator (RT/integrators.cpp:612-815) for a path whose closest hit
 // is h: emission / MIS, Beer absorption, Fresnel, reflect / refract / diffuse with NEE (the
 // shadow ray is returned, not traced) and Russian roulette.  Shared by k_shade (one bounce per
@@ -2290,11 +2334,43 @@ RT_D bool shade_bounce_gt(const DevScene& sc, const rt_settings& st, const Hit& 
 // ENV: rt_set_env_sampling on, the scene has an environment map and NEE is on
 // INTEG: the rt_integrator the bounce is one of (shade_bounce, or shade_bounce_gt for the others, which
 // queue no shadow ray: their instantiations drop the NEE staging below)
-template <bool IN_LDS, bool ENV, int INTEG = RT_INTEGRATOR_ADVANCED>
+//
+// RAMP (r09, the Advanced integrator): the instantiation the iterations near the frame's end carry.  While
+// Counters::ramp is clear it is the kernel above.  In a ramp iteration (every sample claimed, the drain not
+// fused: the pool holds pool.n - gen_free paths at the fronts of the waves, fewer every bounce) wave j of
+// the launch shades the alive paths of ranks [64j, 64j + 64) with every lane busy, and the blocks past the
+// last rank leave at once; the slot-ordered form ran the whole bounce in every wave for its shrinking
+// front.  Only the loads follow the rank (`src`: the state, the path record, the material stack); whatever
+// the thread writes or names is its own slot's, as ever, so the survivors land at the fronts of the first
+// waves of the other buffer, in the layout every kernel expects, and the next ramp iteration is dense again.
+// A path's bits do not depend on its slot (the records are keyed by sample).
+template <bool IN_LDS, bool ENV, int INTEG = RT_INTEGRATOR_ADVANCED, bool RAMP = false>
 __global__ void __launch_bounds__(BLOCK) RT_SHADE_ATTR k_shade(DevScene sc_g, rt_settings st, FrameParams fp, Pool pool,
                                                  Counters* cnt, int cur, int sparse, int fuse) {
-    if (fuse && cnt->fused) return;                 // k_drain runs this iteration's paths (uniform)
     const uint32_t slot = blockIdx.x*blockDim.x + threadIdx.x;
+    if (fuse && cnt->fused) {                       // k_drain runs this iteration's paths (uniform)
+        // (nothing is alive after it: this parity's free counts say so, whatever an earlier k_shade left)
+        if (slot < pool.n && (slot & 63u) == 0) pool.free_w[slot >> 6] = 64;
+        return;
+    }
+    uint32_t src_ = slot;
+    if constexpr (RAMP) {
+        if (cnt->ramp) {                                                // uniform
+            const uint32_t alive = pool.n - cnt->gen_free;
+            // a whole block leaves, before the scene copy's barrier: its waves keep nothing and finish nothing
+            if (blockIdx.x*(uint32_t)BLOCK >= alive) {
+                if (slot < pool.n && (slot & 63u) == 0) { pool.free_w[slot >> 6] = 64; pool.fin_w[slot >> 6] = 0; }
+                return;
+            }
+            const uint32_t r0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(slot & ~63u));
+            src_ = pool.n;                                              // past the last rank: no path
+            if (r0 < alive) {                                           // wave-uniform
+                const uint32_t s = rank_to_slot(pool, pool.n / BLOCK, r0, __lane_id(), slot < alive);
+                if (slot < alive) src_ = s;
+            }
+        }
+    }
+    const uint32_t src = src_;                      // the slot the thread's path is read from
     // The slot's state and path record are loaded before the scene copy, whatever the
     // state: the three round trips (state, record, LDS blob) overlap instead of running
     // back to back.  A slot not traced this iteration (~1/6 of the pool) reads 120 B for nothing.
@@ -2306,9 +2382,9 @@ __global__ void __launch_bounds__(BLOCK) RT_SHADE_ATTR k_shade(DevScene sc_g, rt
     uint4 r4 = {};
     float hw = 0.0f;
     auto load_path = [&]() {
-        o4 = ldnt(&pool.ray_o[slot]); d4 = ldnt(&pool.ray_d[slot]);
-        t4 = ldnt(&pool.thr[slot]); L4 = ldnt(&pool.L[slot]); pn2 = ldnt(&pool.prev_n[slot]);
-        h4 = ldnt(&pool.hit[slot]); r4 = ldnt(&pool.rng[slot]); hw = ldnt(&pool.hit_w[slot]);
+        o4 = ldnt(&pool.ray_o[src]); d4 = ldnt(&pool.ray_d[src]);
+        t4 = ldnt(&pool.thr[src]); L4 = ldnt(&pool.L[src]); pn2 = ldnt(&pool.prev_n[src]);
+        h4 = ldnt(&pool.hit[src]); r4 = ldnt(&pool.rng[src]); hw = ldnt(&pool.hit_w[src]);
     };
     if (sparse) {
         if (cnt->done) {                                                // uniform: every block reads it
@@ -2318,14 +2394,15 @@ __global__ void __launch_bounds__(BLOCK) RT_SHADE_ATTR k_shade(DevScene sc_g, rt
             // paths left it, splatted already, and the k_generate after next would splat it again (float
             // atomics: added twice; records: rewritten alike).  Empty it.
             if (INTEG != RT_INTEGRATOR_ADVANCED && slot < pool.n && (slot & 63u) == 0) pool.fin_w[slot >> 6] = 0;
+            if (slot < pool.n && (slot & 63u) == 0) pool.free_w[slot >> 6] = 64;   // as the fused exit above
             return;
         }
-        if (slot < pool.n) {
-            state0 = pool.state[slot];
+        if (src < pool.n) {
+            state0 = pool.state[src];
             if (state0 != S_FREE) load_path();
         }
-    } else if (slot < pool.n) {
-        state0 = pool.state[slot];
+    } else if (src < pool.n) {
+        state0 = pool.state[src];
         load_path();
     }
     if (state0 == S_NEW) {                              // a camera ray (k_generate)
@@ -2333,7 +2410,7 @@ __global__ void __launch_bounds__(BLOCK) RT_SHADE_ATTR k_shade(DevScene sc_g, rt
         state0 = S_TRACE;
     }
     const DevScene sc = scene_in_lds<IN_LDS>(sc_g, lds_scene);
-    const bool valid = slot < pool.n && state0 == S_TRACE;             // traced this iteration
+    const bool valid = src < pool.n && state0 == S_TRACE;              // traced this iteration
     bool cont = false, done = false, shadow = false, cast_shadow = false, enq = false;
     Prologue spro = {}, cpro = {};
     V3 nro = {0, 0, 0}, nrd = {0, 0, 0};
@@ -2343,7 +2420,7 @@ __global__ void __launch_bounds__(BLOCK) RT_SHADE_ATTR k_shade(DevScene sc_g, rt
     uint32_t nslot = 0;                                                // a survivor's slot in pool.nx
     // finished-array entries (see the tail): the slots k_generate made finished, then the paths
     // that end here
-    const bool made_fin = slot < pool.n && state0 == S_DONE;
+    const bool made_fin = src < pool.n && state0 == S_DONE;
     const unsigned long long made_fin_mask = __ballot(made_fin);
     // pixel, sample key, vignette and tile-list pixel (`meta`): written out only at the end, so they
     // wait in LDS (the thread's own entry, no barrier) instead of registers across the bounce and
@@ -2369,7 +2446,7 @@ __global__ void __launch_bounds__(BLOCK) RT_SHADE_ATTR k_shade(DevScene sc_g, rt
         Hit h;
         h.t = h4.x; h.code = __float_as_uint(h4.y); h.tri = __float_as_uint(h4.z); h.v = h4.w; h.w = hw;
         if constexpr (INTEG == RT_INTEGRATOR_ADVANCED)
-            done = shade_bounce<ENV>(sc, st, ss, pool, slot, h, ro, rd, thr, total, prev_pdf, bounce, is_spec, at, rng,
+            done = shade_bounce<ENV>(sc, st, ss, pool, src, h, ro, rd, thr, total, prev_pdf, bounce, is_spec, at, rng,
                                      cast_shadow, sh_o, sh_d, sh_c, sh_t, sh_light);
         else
             done = shade_bounce_gt<INTEG>(sc, st, h, ro, rd, thr, total, bounce, rng);
@@ -2393,7 +2470,7 @@ __global__ void __launch_bounds__(BLOCK) RT_SHADE_ATTR k_shade(DevScene sc_g, rt
             pool.nx.state[nslot] = S_TRACE;
             // the material stack moves with the path (levels 1..at; level 0 is the implicit air)
             for (int32_t lv = 1; lv <= at; ++lv)
-                pool.nx.mstack[(size_t)lv*pool.n + nslot] = pool.mstack[(size_t)lv*pool.n + slot];
+                pool.nx.mstack[(size_t)lv*pool.n + nslot] = pool.mstack[(size_t)lv*pool.n + src];
         }
         const unsigned long long fm = made_fin_mask | __ballot(done);
         if (done) {                                        // everything but total_color
@@ -2441,7 +2518,7 @@ __global__ void __launch_bounds__(BLOCK) RT_SHADE_ATTR k_shade(DevScene sc_g, rt
     const uint32_t fidx = (slot & ~63u) + (uint32_t)__popcll(fmask & ((1ull << __lane_id()) - 1ull));
     if (made_fin) {                                 // L = 0 with the vignette in .w (k_generate)
         const uint4 fmeta = stash[threadIdx.x];
-        stnt(&pool.fin_L[fidx], pool.L[slot]);
+        stnt(&pool.fin_L[fidx], pool.L[src]);
         stnt(&pool.fin_k[fidx], make_uint2(fmeta.y, fmeta.w));
         stnt(&pool.fin_px[fidx], fmeta.x);
     }
@@ -2550,7 +2627,7 @@ __global__ void __launch_bounds__(BLOCK) k_drain_list(DevScene sc, rt_settings s
         splat_sample(fp, pool, ld3(fl), fl.w, make_float2(j.x, j.y), fk.x, fk.y);
     }
     if (slot < pool.n && (slot & 63u) == 0) {
-        pool.fin_w[slot >> 6] = 0; pool.fin2_w[slot >> 6] = 0; pool.free_w[slot >> 6] = 64;
+        pool.fin_w[slot >> 6] = 0; pool.fin2_w[slot >> 6] = 0; pool.free_w[slot >> 6] = 64; pool.free_p[slot >> 6] = 64;
     }
     if (slot == 0) cnt->drained = 1;
     const uint32_t shard = blockIdx.x % NSHARD;
@@ -3431,11 +3508,13 @@ __global__ void __launch_bounds__(BK_THREADS) k_bookkeep(Counters* cnt, Pool poo
             sp = plan.merged ? cnt->shadow_count[cur][t][0] : 0u;
         }
         unsigned long long next = 0, total = 0, lim = 0, start = 0;
-        uint32_t gfree = 0, it = 0, rcur = 0, us_prev = 0, drained = 0;
+        uint32_t gfree = 0, it = 0, rcur = 0, us_prev = 0, drained = 0, r_it = 0;
+        unsigned long long r_paths = 0;
         if (t == 0 && it_phase) {
             next = cnt->next_sample; total = cnt->total_samples; lim = cnt->claim_limit;
             start = cnt->start_sample; gfree = cnt->gen_free; it = cnt->iter; rcur = cnt->res_cursor;
             us_prev = cnt->unsplat_prev; drained = cnt->drained;
+            r_it = cnt->ramp_iters; r_paths = cnt->ramp_paths;
         }
         // the claim cursor `life` iterations ago (loaded before any store to the counters)
         const unsigned long long done_cursor =
@@ -3488,8 +3567,14 @@ __global__ void __launch_bounds__(BK_THREADS) k_bookkeep(Counters* cnt, Pool poo
                 cnt->unsplat_prev = ps;
                 // nothing left to claim, trace or splat: every record is in the ring
                 const bool complete = next >= total && pend == 0 && ps == 0 && prev == 0 && spn == 0;
+                const bool fusing = !complete && plan.fuse && next >= total && pend <= plan.fuse;
                 if (complete) cnt->done = 1;
-                else if (plan.fuse && next >= total && pend <= plan.fuse) cnt->fused = 1;
+                else if (fusing) cnt->fused = 1;
+                // the ramp-down: the next k_shade finds `pend` paths at the waves' fronts and no new one (the
+                // claims have ended, not just met the ring's limit); cleared with done or fused
+                const bool ramp = !complete && !fusing && next >= total && plan.cast0 && pend != 0;
+                cnt->ramp = ramp ? 1u : 0u;
+                if (ramp) { cnt->ramp_iters = r_it + 1u; cnt->ramp_paths = r_paths + pend; }
                 cnt->iter = it + 1;
                 cnt->hist[it & 127u] = next;
                 if (plan.mode) {
@@ -3697,7 +3782,8 @@ struct rt_scene {
     // traced shadow rays per traced extension ray in this scene's last frame (-1: none yet): the
     // shadow-launch policy's input (rt_scene_config::shadow_launch, AUTO)
     double shadow_share = -1.0;
-    float4* d_samp = nullptr;       // per-sample records for the deterministic splat
+    uint64_t ramp_iters = 0, ramp_paths = 0;   // the last frame's ramp-down (rt_scene_ramp_stats)
+    float4* d_samp = nullptr;      // per-sample records for the deterministic splat
     float* d_samp_jy = nullptr;
     size_t samp_cap = 0;
     float* d_lut = nullptr;
@@ -3924,6 +4010,7 @@ int ensure_pool(Partition& pt, uint32_t n) {
     e |= alloc((void**)&p.claim_base, 4*nblocks);
     e |= alloc((void**)&p.fin_w, 4*(N / 64));
     e |= alloc((void**)&p.free_w, 4*(N / 64));
+    e |= alloc((void**)&p.free_p, 4*(N / 64));
     e |= alloc((void**)&p.fin_L, 16*N);
     e |= alloc((void**)&p.fin_k, 8*N);
     e |= alloc((void**)&p.fin_px, 4*N);
@@ -3971,6 +4058,7 @@ Pool pool_view(const Pool& p, int par) {
     std::swap(v.rng, v.nx.rng); std::swap(v.hit, v.nx.hit); std::swap(v.hit_w, v.nx.hit_w);
     std::swap(v.mstack, v.nx.mstack); std::swap(v.state, v.nx.state);
     std::swap(v.fin_L, v.fin2_L); std::swap(v.fin_k, v.fin2_k); std::swap(v.fin_px, v.fin2_px); std::swap(v.fin_w, v.fin2_w);
+    std::swap(v.free_w, v.free_p);
     return v;
 }
 
@@ -4118,13 +4206,17 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
     uint64_t klaunch[RT_KERNEL_COUNT] = {};
     // (a recursive integrator's sample is splatted by the k_recurse of the iteration that claimed it)
     const uint32_t life = recursive ? 1u : std::max<uint32_t>(st->max_bounce_count, 1u);
-    // live paths at which the drain is fused (k_drain): 2.5 times its grid's lanes, or a tenth of the
-    // pool if more (r02 sweeps: rank 0 of 8, 3.3M-path pools: 1x the lanes 40.5 ms, 2.5x 39.3, 4.5x 40.0,
-    // 9x 41.0; the full frame's 8.4M-path pools: 2.5x 235.8, 600k 234.1-235.2, 1M 234.2-234.3 ms);
-    // rt_scene_config::fuse_paths another count (0 = never)
+    // rt_scene_config::ramp_shade: the dense ramp-down k_shade (0 = auto: on)
+    const bool ramp_shade = advanced && s->cfg.ramp_shade != 2;
+    // live paths at which the drain is fused (k_drain): 2.5 times its grid's lanes (r02 sweep, rank 0 of 8,
+    // 3.3M-path pools: 1x the lanes 40.5 ms, 2.5x 39.3, 4.5x 40.0, 9x 41.0).  With the slot-ordered ramp
+    // (ramp_shade off) a tenth of the pool if that is more (r02, the full frame's 8.4M-path pools: 2.5x 235.8,
+    // 600k 234.1-235.2, 1M 234.2-234.3 ms); the dense ramp iterations beat k_drain per path further down
+    // (r09, profiles/r09_fuse_sweep.txt: C3 200.9 ms at pool/10, 198.7 at pool/20, 196.9 at pool/40,
+    // 196.2 at 2.5x the lanes alone).  rt_scene_config::fuse_paths another count (0 = never)
     const uint32_t fuse_paths = !advanced ? 0u : s->cfg.fuse_paths >= 0
         ? (uint32_t)std::min<int64_t>(s->cfg.fuse_paths, 0xFFFFFFFFll)
-        : std::max(s->drain_lanes_full*5u/2u, pool_n / 10u);
+        : ramp_shade ? s->drain_lanes_full*5u/2u : std::max(s->drain_lanes_full*5u/2u, pool_n / 10u);
     for (int k = 0; k < nparts; ++k) {
         int err = ensure_partition(s, k);
         if (!err) err = ensure_pool(s->part[k], pool_n);
@@ -4172,6 +4264,7 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
         HIP_OK(hipMemsetAsync(pt.pool.fin_w, 0, 4ull*N / 64, r.stream));
         HIP_OK(hipMemsetAsync(pt.pool.fin2_w, 0, 4ull*N / 64, r.stream));
         HIP_OK(hipMemsetD32Async((hipDeviceptr_t)pt.pool.free_w, 64, N / 64, r.stream));
+        HIP_OK(hipMemsetD32Async((hipDeviceptr_t)pt.pool.free_p, 64, N / 64, r.stream));
         launch_bookkeep(pt.cnt, pt.pool, r.grid, 0, BK_FIRST, ResPlan{}, r.stream);
         if (prof && !pt.events) {
             for (auto& e : pt.ev) HIP_OK(hipEventCreate(&e));
@@ -4329,6 +4422,18 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
             shade_gt(std::integral_constant<int, RT_INTEGRATOR_NORMALS>{});
         } else if (integ == RT_INTEGRATOR_DISTANCES) {
             shade_gt(std::integral_constant<int, RT_INTEGRATOR_DISTANCES>{});
+        } else if (ramp_shade && r.near) {
+            // near the frame's end: the ramp-capable instantiation (one launch: it is the standard kernel
+            // while Counters::ramp is clear, so any mix with the launches above is safe)
+            constexpr int ADV = RT_INTEGRATOR_ADVANCED;
+            if (env) {
+                if (ds.blob_q) k_shade<true, true, ADV, true><<<r.grid, BLOCK, 16*ds.blob_q, q>>>(ds, *st, fp, pv, pt.cnt, r.cur, sparse, fuse);
+                else k_shade<false, true, ADV, true><<<r.grid, BLOCK, 0, q>>>(ds, *st, fp, pv, pt.cnt, r.cur, sparse, fuse);
+            } else if (ds.blob_q) {
+                k_shade<true, false, ADV, true><<<r.grid, BLOCK, 16*ds.blob_q, q>>>(ds, *st, fp, pv, pt.cnt, r.cur, sparse, fuse);
+            } else {
+                k_shade<false, false, ADV, true><<<r.grid, BLOCK, 0, q>>>(ds, *st, fp, pv, pt.cnt, r.cur, sparse, fuse);
+            }
         } else if (env) {
             if (ds.blob_q) k_shade<true, true><<<r.grid, BLOCK, 16*ds.blob_q, q>>>(ds, *st, fp, pv, pt.cnt, r.cur, sparse, fuse);
             else k_shade<false, true><<<r.grid, BLOCK, 0, q>>>(ds, *st, fp, pv, pt.cnt, r.cur, sparse, fuse);
@@ -4470,8 +4575,11 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
     Counters sum = {};
     unsigned long long tv[2*TV_N] = {};
     uint64_t iters = 0;
+    s->ramp_iters = s->ramp_paths = 0;
     for (int k = 0; k < nparts; ++k) {
         const Counters& c = s->part[k].cnt_host[run[k].final_buf];
+        s->ramp_iters += c.ramp_iters;
+        s->ramp_paths += c.ramp_paths;
         sum.closest_rays += c.closest_rays;
         sum.shadow_rays += c.shadow_rays;
         sum.traced_rays[0] += c.traced_rays[0];
@@ -4641,6 +4749,7 @@ int check_config(const rt_scene_config* c) {
     else if (c->traversal_ref != 0 && c->traversal_ref != 1) bad = "traversal_ref";
     else if (c->drain_every < 0 || c->drain_every > 1024) bad = "drain_every (0..1024)";
     else if (c->shadow_launch < RT_SHADOW_LAUNCH_AUTO || c->shadow_launch > RT_SHADOW_LAUNCH_MERGED) bad = "shadow_launch";
+    else if (c->ramp_shade < 0 || c->ramp_shade > 2) bad = "ramp_shade (0..2)";
     if (bad) { set_error(std::string("rt_scene_config: bad ") + bad); return RT_ERROR_INVALID; }
     return RT_OK;
 }
@@ -4688,6 +4797,7 @@ bool config_from_env(rt_scene_config& c) {
     if (num("RT_TRAVERSAL_REF", 0, 1, v)) c.traversal_ref = (int32_t)v;
     if (num("RT_DRAIN_EVERY", 0, 1024, v)) c.drain_every = (int32_t)v;
     if (num("RT_SHADOW_LAUNCH", RT_SHADOW_LAUNCH_AUTO, RT_SHADOW_LAUNCH_MERGED, v)) c.shadow_launch = (int32_t)v;
+    if (num("RT_RAMP_SHADE", 0, 2, v)) c.ramp_shade = (int32_t)v;
     return ok;
 }
 
@@ -5601,20 +5711,24 @@ int rt_debug_mesh_bvh4(const rt_bvh_node* nodes, uint32_t node_count, float* out
 
 // k_generate's claim -> slot mapping on the host: k_bookkeep's scan of the blocks' free counts, then, per
 // wave of 64 claims, claim_to_slot's steps with the lanes as a loop (the same claim_stride / claim_narrow /
-// claim_slot functions, the same probes and rounds).
-int rt_debug_claim_slots(const uint32_t* free_w, uint32_t nwaves, uint32_t first_claim, uint32_t count, uint32_t* out_slots) {
+// claim_slot functions, the same probes and rounds).  `rank`: the ramp k_shade's rank -> slot mapping instead
+// (rank_to_slot: the blocks' keys are their first ranks, rank_key, and rank_slot finds the wave).
+static int debug_map_slots(const uint32_t* free_w, uint32_t nwaves, uint32_t first_claim, uint32_t count, uint32_t* out_slots,
+                           bool rank) {
     if (!free_w || !nwaves || nwaves % (BLOCK / 64) || (count && !out_slots)) { set_error("invalid argument"); return RT_ERROR_INVALID; }
     const uint32_t nblocks = nwaves / (BLOCK / 64);
     std::vector<uint32_t> base(nblocks);
     uint64_t run = 0;
     for (uint32_t b = 0; b < nblocks; ++b) {
-        base[b] = (uint32_t)run;
+        base[b] = rank ? rank_key(b, (uint32_t)run) : (uint32_t)run;
         for (int w = 0; w < BLOCK / 64; ++w) {
             if (free_w[4*b + w] > 64u) { set_error("a wave has at most 64 free slots"); return RT_ERROR_INVALID; }
             run += free_w[4*b + w];
         }
     }
-    if ((uint64_t)first_claim + count > run) { set_error("more claims than free slots"); return RT_ERROR_INVALID; }
+    if (rank) {
+        if ((uint64_t)first_claim + count > (uint64_t)nwaves*64u - run) { set_error("more ranks than alive paths"); return RT_ERROR_INVALID; }
+    } else if ((uint64_t)first_claim + count > run) { set_error("more claims than free slots"); return RT_ERROR_INVALID; }
     auto at_or_max = [&](uint32_t idx, uint32_t end) { return idx < end ? base[idx] : 0xFFFFFFFFu; };
     for (uint32_t done = 0; done < count; done += 64u) {
         const uint32_t c0 = first_claim + done, lanes = std::min(64u, count - done);
@@ -5634,9 +5748,22 @@ int rt_debug_claim_slots(const uint32_t* free_w, uint32_t nwaves, uint32_t first
                 if (at_or_max(at + 1u + 63u, nblocks) <= c) pos = 64u;
                 if (pos < 64u) { b = at + pos; break; }
             }
-            out_slots[done + lane] = claim_slot(b, c - base[b], free_w[4*b], free_w[4*b + 1], free_w[4*b + 2], free_w[4*b + 3]);
+            out_slots[done + lane] = rank ? rank_slot(b, c - base[b], free_w[4*b], free_w[4*b + 1], free_w[4*b + 2])
+                : claim_slot(b, c - base[b], free_w[4*b], free_w[4*b + 1], free_w[4*b + 2], free_w[4*b + 3]);
         }
     }
+    return RT_OK;
+}
+int rt_debug_claim_slots(const uint32_t* free_w, uint32_t nwaves, uint32_t first_claim, uint32_t count, uint32_t* out_slots) {
+    return debug_map_slots(free_w, nwaves, first_claim, count, out_slots, false);
+}
+int rt_debug_rank_slots(const uint32_t* free_w, uint32_t nwaves, uint32_t first_rank, uint32_t count, uint32_t* out_slots) {
+    return debug_map_slots(free_w, nwaves, first_rank, count, out_slots, true);
+}
+int rt_scene_ramp_stats(const rt_scene* s, uint64_t* out_iterations, uint64_t* out_paths) {
+    if (!s || !out_iterations || !out_paths) { set_error("null argument"); return RT_ERROR_INVALID; }
+    *out_iterations = s->ramp_iters;
+    *out_paths = s->ramp_paths;
     return RT_OK;
 }
 

@@ -398,6 +398,17 @@ int rt_debug_top_sequences(const rt_bvh_node* nodes, uint32_t node_count, uint32
  * first_claim on.  RT_ERROR_INVALID when the range passes the free slots. */
 int rt_debug_claim_slots(const uint32_t* free_w, uint32_t nwaves, uint32_t first_claim, uint32_t count,
                          uint32_t* out_slots);
+/* The mirror of it, the rank -> slot mapping of the dense ramp-down shade (host only): the same
+ * pool, whose alive paths are wave w's first 64 - free_w[w] slots, ranked in slot order.  Writes
+ * the slots of the ranks [first_rank, first_rank + count), found the way the shade kernel finds
+ * them, in waves of 64 ranks from first_rank on.  RT_ERROR_INVALID when the range passes the
+ * alive paths. */
+int rt_debug_rank_slots(const uint32_t* free_w, uint32_t nwaves, uint32_t first_rank, uint32_t count,
+                        uint32_t* out_slots);
+/* The ramp-down of the scene's last frame, summed over its partitions: the shade iterations that
+ * ran after the last sample was claimed and before the fused drain (or the frame's end), and the
+ * paths they shaded.  iterations x the path pool - paths is the slots those launches found empty. */
+int rt_scene_ramp_stats(const rt_scene* scene, uint64_t* out_iterations, uint64_t* out_paths);
 
 /* Exhaustive check of the kernels' fast reciprocal (3 instructions instead of the
  * division expansion) against the correctly rounded IEEE 1.0f / x on `device`: every
@@ -504,7 +515,8 @@ int rt_cancel(rt_scene* scene);
  * Two scenes in one process may differ.  rt_scene_upload starts a scene from
  * rt_scene_default_config(), then applies the test-override environment variables once
  * (RT_SPLAT, RT_PARTITIONS, RT_FUSE_PATHS, RT_SPLAT_CHUNK, RT_SPLAT_RING,
- * RT_SAMPLE_BUDGET_GB, RT_RES_TALL_PIXELS, RT_DEBUG_TRAVERSAL, RT_DRAIN_EVERY, RT_SHADOW_LAUNCH);
+ * RT_SAMPLE_BUDGET_GB, RT_RES_TALL_PIXELS, RT_DEBUG_TRAVERSAL, RT_DRAIN_EVERY, RT_SHADOW_LAUNCH,
+ * RT_RAMP_SHADE);
  * nothing reads the
  * environment per frame.  A field at RT_CONFIG_INHERIT follows the process-wide setter
  * above at each frame (rt_set_splat_mode / rt_set_shard_mode / rt_set_env_sampling /
@@ -542,7 +554,10 @@ typedef struct rt_scene_config {
                                        schedule knob for the tests: frames are identical for every N */
     int32_t  shadow_launch;         /* (ABI 8) rt_shadow_launch: where the NEE shadow rays are traced.
                                        Frames are identical for every value */
-    int32_t  reserved[4];
+    int32_t  ramp_shade;            /* (one of ABI 8's reserved words) the dense shade launch of a frame's
+                                       ramp-down, once every sample is claimed: 0 = auto (on), 1 = on,
+                                       2 = off.  Frames are identical for every value */
+    int32_t  reserved[3];
 } rt_scene_config;
 int rt_scene_default_config(rt_scene_config* out);
 int rt_scene_get_config(const rt_scene* scene, rt_scene_config* out);
