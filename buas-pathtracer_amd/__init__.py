@@ -331,6 +331,13 @@ class DeviceScene:
         _check(lib().rt_scene_ramp_stats(self._h, C.byref(it), C.byref(paths)))
         return int(it.value), int(paths.value)
 
+    def stack_depth(self):
+        """rt_scene_stack_depth: (entries, entries with traversal_ref's markers) the upload's bound says a
+        traversal of this scene can hold; rt_scene_upload requires entries + 2 <= 64."""
+        d, r = C.c_uint32(0), C.c_uint32(0)
+        _check(lib().rt_scene_stack_depth(self._h, C.byref(d), C.byref(r)))
+        return int(d.value), int(r.value)
+
     def configure(self, **fields):
         """rt_scene_set_config with the named fields changed, e.g. configure(partitions=1,
         splat_mode=abi.RT_SPLAT_EXACT).  Returns the previous configuration (pass it to

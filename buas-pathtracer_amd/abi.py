@@ -236,6 +236,7 @@ ABI_FUNCTIONS = {
     "rt_scene_default_config": (C.c_int, [P(SceneConfig)]),
     "rt_scene_get_config": (C.c_int, [C.c_void_p, P(SceneConfig)]),
     "rt_scene_set_config": (C.c_int, [C.c_void_p, P(SceneConfig)]),
+    "rt_scene_stack_depth": (C.c_int, [C.c_void_p, P(C.c_uint32), P(C.c_uint32)]),
     "rt_postprocess_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, P(PostSettings), C.c_uint32,
                                         C.c_void_p, C.c_void_p]),
     "rt_postprocess": (C.c_int, [C.c_int, P(AccumulationBuffer), P(PostSettings), C.c_uint32, P(C.c_uint32)]),

@@ -362,8 +362,11 @@ RT_D void object_ray(float4 q0, float4 q1, float4 q2, bool translate, bool plain
 // test (ray_intersect_bounding_volume, :107-133) split in two.
 //
 // Stack: per-lane, STACK_LDS entries in LDS ([level][lane], bank-conflict
-// free), deeper levels spill to a per-thread global area.  Total depth 64 =
-// the reference's node_stack[64] (:261, :445).
+// free), deeper levels spill to a per-thread global area.  Total depth 64, the
+// size of the reference's node_stack[64] (:261, :445); a BVH4 walk holds up to 3
+// entries per two BVH2 levels, so rt_scene_upload bounds the entries itself
+// (top_depth + mesh_depth + 2 <= 64, rt_scene_stack_depth) and refuses some
+// BVH2s the reference walks (tests/test_deep_bvh.py).
 // ----------------------------------------------------------------------
 constexpr int STACK_DEPTH = 64;
 constexpr int STACK_LDS = 16;
@@ -4817,6 +4820,13 @@ int rt_scene_get_config(const rt_scene* s, rt_scene_config* out) {
     return RT_OK;
 }
 
+int rt_scene_stack_depth(const rt_scene* s, uint32_t* out_depth, uint32_t* out_depth_ref) {
+    if (!s || !out_depth || !out_depth_ref) { set_error("null argument"); return RT_ERROR_INVALID; }
+    *out_depth = s->bvh_depth;
+    *out_depth_ref = s->bvh_depth_ref;
+    return RT_OK;
+}
+
 int rt_scene_set_config(rt_scene* s, const rt_scene_config* c) {
     if (!s || !c) { set_error("null argument"); return RT_ERROR_INVALID; }
     int err = check_config(c);
@@ -5075,7 +5085,13 @@ int rt_scene_upload(const rt_scene_desc* d, int device, rt_scene** out) {
         ds.finite_boxes = (within(d->bvh_nodes, d->bvh_node_count) && within(mnodes.data(), mnodes.size())) ? 1u : 0u;
     }
     if (top_depth + mesh_depth + 2 > STACK_DEPTH) {
-        set_error("BVH too deep for the 64-entry traversal stack (RT/intersection.cpp:445)");
+        // the device's own bound: a BVH4 level can hold 3 entries where the BVH2's two levels hold 2, so a
+        // BVH2 that the reference's node_stack[64] (RT/intersection.cpp:445) walks may be refused here
+        char msg[224];
+        snprintf(msg, sizeof(msg), "rt_scene_upload: BVH too deep for the device's BVH4 traversal stack: needs %u entries "
+                 "(top level %u + mesh BVH4 %u + 2), %d available (the device's bound, not the reference's BVH2 stack)",
+                 top_depth + mesh_depth + 2, top_depth, mesh_depth, STACK_DEPTH);
+        set_error(msg);
         return fail(RT_ERROR_INVALID);
     }
     s->bvh_depth = top_depth + mesh_depth;

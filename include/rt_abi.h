@@ -563,6 +563,17 @@ int rt_scene_default_config(rt_scene_config* out);
 int rt_scene_get_config(const rt_scene* scene, rt_scene_config* out);
 int rt_scene_set_config(rt_scene* scene, const rt_scene_config* config);
 
+/* The traversal stack entries the scene's BVHs can need, as rt_scene_upload bounds them (read-only):
+ * out_depth = top_depth + mesh_depth, where top_depth is the depth of the top-level BVH2 and mesh_depth the
+ * largest bound over the meshes' BVH4s (a BVH4 node leaves up to 3 entries behind while its fourth child is
+ * walked, so up to 3 per two BVH2 levels); out_depth_ref the same for a walk in the reference's units
+ * (rt_scene_config::traversal_ref), which adds a marker per BVH4 level.  The stack holds 64 entries:
+ * rt_scene_upload refuses a scene with out_depth + 2 > 64, and traversal_ref is refused when
+ * out_depth_ref + 2 > 64.  This is the device's own bound: the reference's node_stack[64]
+ * (RT/intersection.cpp:445) holds BVH2 entries, at most one per level, so it walks some BVH2s (from depth 43
+ * on) that are refused here. */
+int rt_scene_stack_depth(const rt_scene* scene, uint32_t* out_depth, uint32_t* out_depth_ref);
+
 #ifdef __cplusplus
 }
 #endif
