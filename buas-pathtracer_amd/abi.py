@@ -35,6 +35,7 @@ RT_RNG_PER_SAMPLE, RT_RNG_TILE_STREAM = 0, 1
 RT_HIT_MISS = 0xFFFFFFFF
 RT_HIT_PLANE_BIT = 0x80000000
 RTH_BVH_MIDPOINT_SPLIT, RTH_BVH_SAH_BINNED, RTH_BVH_SAH_FULL = range(3)
+RT_BVH_BUILD_MIDPOINT, RT_BVH_BUILD_SAH_BINNED, RT_BVH_BUILD_SAH_FULL = range(3)   # rt_bvh_build_method
 
 RT_KERNEL_NAMES = ("generate", "extend", "shade", "connect", "splat", "resolve")
 RT_KERNEL_COUNT = 6

@@ -682,12 +682,13 @@ uint32_t rth_add_mesh(rth_scene* s, uint32_t mat, uint32_t mesh_id, const rt_m4x
 }
 
 // The BVH builder the scene model uses: the host restatement, or (rth_set_bvh_device) the
-// device builder rt_build_bvh for the methods it has (midpoint, binned SAH), bit-identical.
+// device builder rt_build_bvh (midpoint, binned SAH, full SAH), bit-identical.
 static int g_bvh_device = -1;
 void rth_set_bvh_device(int device) { g_bvh_device = device; }
 
 static int build_entries(std::vector<SortEntry>& in, int method, std::vector<rt_bvh_node>& nodes) {
-    if (g_bvh_device >= 0 && in.size() > 0 && (method == RTH_BVH_MIDPOINT_SPLIT || method == RTH_BVH_SAH_BINNED)) {
+    if (g_bvh_device >= 0 && in.size() > 0 &&
+        (method == RTH_BVH_MIDPOINT_SPLIT || method == RTH_BVH_SAH_BINNED || method == RTH_BVH_SAH_FULL)) {
         const size_t n = in.size();
         std::vector<rt_v3> p(n), r(n);
         for (size_t i = 0; i < n; ++i) { p[i] = rv(in[i].p); r[i] = rv(in[i].r); }
@@ -695,7 +696,8 @@ static int build_entries(std::vector<SortEntry>& in, int method, std::vector<rt_
         std::vector<uint32_t> order(n);
         uint32_t count = 0;
         const int err = rt_build_bvh(g_bvh_device, (uint32_t)n, p.data(), r.data(),
-                                     method == RTH_BVH_MIDPOINT_SPLIT ? RT_BVH_BUILD_MIDPOINT : RT_BVH_BUILD_SAH_BINNED,
+                                     method == RTH_BVH_MIDPOINT_SPLIT ? RT_BVH_BUILD_MIDPOINT :
+                                     method == RTH_BVH_SAH_FULL ? RT_BVH_BUILD_SAH_FULL : RT_BVH_BUILD_SAH_BINNED,
                                      nodes.data(), &count, order.data());
         if (err) { set_err(std::string("rt_build_bvh: ") + rt_build_bvh_last_error()); return err; }
         nodes.resize(count);

@@ -433,8 +433,10 @@ int rt_postprocess(int device, const rt_accumulation_buffer* accum, const rt_pos
                    uint32_t total_frame_index, uint32_t* out_bgra);
 
 /* The reference's top-down BVH builders on the device (RT/bvh.cpp:222-326 with
- * partition_midpoint :53-61 or partition_sah_binned :138-213, the partition of :26-51):
- * one launch per tree level, one workgroup per node.  Bit-identical to the sequential
+ * partition_midpoint :53-61, partition_sah_binned :138-213 or the full SAH sweep
+ * partition_objects_sah / evaluate_sah :63-131, the partition of :26-51): one launch per
+ * tree level and one workgroup per node; the full sweep runs three launches per level and
+ * spreads each node's candidate splits over workgroups.  Bit-identical to the sequential
  * recursion: out_nodes holds the reference's BVHNode array (root 0, node 1 padding,
  * children pairs in its order; capacity 2n + 2 nodes), out_order[i] the entry index at
  * position i of the partitioned entry array (BVHSortEntry::index).  Entries are the
@@ -443,6 +445,7 @@ int rt_postprocess(int device, const rt_accumulation_buffer* accum, const rt_pos
 enum rt_bvh_build_method {
     RT_BVH_BUILD_MIDPOINT   = 0,    /* BVH_MidpointSplit */
     RT_BVH_BUILD_SAH_BINNED = 1,    /* BVH_SAHBinned (16 bins) */
+    RT_BVH_BUILD_SAH_FULL   = 2,    /* BVH_SAHFull: every entry's centre is a candidate split */
 };
 int rt_build_bvh(int device, uint32_t n, const rt_v3* p, const rt_v3* r, int method,
                  rt_bvh_node* out_nodes, uint32_t* out_node_count, uint32_t* out_order);

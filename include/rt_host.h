@@ -94,7 +94,7 @@ int      rth_load_environment_map(rth_scene* s, const char* hdr_path);
 int      rth_set_environment_map(rth_scene* s, uint32_t w, uint32_t h, const rt_v3* pixels);
 
 /* Build the BVHs of rth_create_mesh / rth_create_scene_bvh on `device` with rt_build_bvh
- * (midpoint and binned SAH; bit-identical to the host builder); -1 (the default): on the host.
+ * (all three methods; bit-identical to the host builder); -1 (the default): on the host.
  * rth_build_bvh_entries: the builder on raw BVHSortEntry boxes (centre p, half extent r),
  * with the same outputs as rt_build_bvh; uses the device when one was set.  Returns an
  * rt_status. */
