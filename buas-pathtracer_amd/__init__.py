@@ -22,13 +22,14 @@ import numpy as np
 
 from . import abi
 from .abi import (V3, v3, M4x4Inv, Material, Camera, Settings, FilterCache, PostSettings, TileSet, Stats,
-                  AccumulationBuffer, RayQuery, HitRecord, BvhInfo)
+                  AccumulationBuffer, RayQuery, HitRecord, BvhInfo, DenoiseParams)
 
 __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settings", "load_reconstruction_kernel",
            "translate", "scale", "rotate_x", "rotate_y", "rotate_z", "identity", "aim_camera", "aim_camera_at",
            "recompute_camera", "resolve_bgra8", "postprocess", "write_bitmap", "lib", "abi", "v3", "PI_32", "DEG_TO_RAD",
            "set_splat_mode", "splat_mode", "take_picture", "read_bitmap", "integrator_name", "find_integrator",
-           "integrator_supported", "scene_integrator_supported"]
+           "integrator_supported", "scene_integrator_supported", "DenoiseParams", "default_denoise_params", "denoise",
+           "denoise_workspace_bytes"]
 
 PI_32 = 3.14159265359
 DEG_TO_RAD = 6.28318530717 / 360.0
@@ -338,6 +339,34 @@ class DeviceScene:
         _check(lib().rt_scene_stack_depth(self._h, C.byref(d), C.byref(r)))
         return int(d.value), int(r.value)
 
+    def render_guides(self, camera, settings, filter_cache, w, h, spp, total_frame_index=0, tile=64):
+        """The two guide frames of the denoise stage: a Normals and a Distances frame (integrators 4 and 5) of
+        `spp` samples per pixel with the caller's other settings -> (normals, distances), host float32
+        [h, w, 4] accumulation buffers for denoise(accum, normals, distances)."""
+        st = Settings.from_buffer_copy(settings)
+        st.samples_per_pixel = spp
+        out = []
+        for integrator in (abi.RT_INTEGRATOR_NORMALS, abi.RT_INTEGRATOR_DISTANCES):
+            st.integrator = integrator
+            out.append(self.render(camera, st, filter_cache, w, h, total_frame_index=total_frame_index, tile=tile)[0])
+        return out[0], out[1]
+
+    def render_picture_denoised(self, camera, settings, filter_cache, w, h, post, params=None, guide_spp=0,
+                                total_frame_index=0, tile=64, shard_index=0, shard_count=1):
+        """rt_render_picture_denoised: the frame of rt_render_picture with the denoise stage between the
+        accumulation buffer and the output pass, guided by a Normals and a Distances frame of `guide_spp`
+        samples per pixel (0: the beauty frame's count) -> (BGRA8 (h, w) u32, the beauty frame's stats)."""
+        if params is None:
+            params = default_denoise_params()
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        out = np.zeros((h, w), np.uint32)
+        stats = Stats()
+        _check(lib().rt_render_picture_denoised(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                                C.byref(tiles), total_frame_index, w, h, C.byref(post),
+                                                C.byref(params), guide_spp,
+                                                out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(stats)))
+        return out, stats
+
     def configure(self, **fields):
         """rt_scene_set_config with the named fields changed, e.g. configure(partitions=1,
         splat_mode=abi.RT_SPLAT_EXACT).  Returns the previous configuration (pass it to
@@ -386,6 +415,44 @@ def postprocess(accum, post, total_frame_index=0, device=0):
     buf = AccumulationBuffer(w, h, 0, accum.ctypes.data_as(C.POINTER(C.c_float)))
     _check(lib().rt_postprocess(device, C.byref(buf), C.byref(post), total_frame_index,
                                 out.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return out
+
+
+def default_denoise_params():
+    """rt_denoise_default_params (no device needed) -> DenoiseParams."""
+    p = DenoiseParams()
+    _check(lib().rt_denoise_default_params(C.byref(p)))
+    return p
+
+
+def denoise_workspace_bytes(w, h):
+    """rt_denoise_workspace_bytes (no device needed): 64 bytes per pixel."""
+    return int(lib().rt_denoise_workspace_bytes(w, h))
+
+
+def denoise(accum, guide0=None, guide1=None, params=None, device=0):
+    """The denoise stage on the GPU (rt_denoise): host float4 accumulation buffers (h, w, 4) in -- the beauty
+    frame and up to two guide frames, e.g. DeviceScene.render_guides' -- and the filtered buffer out, which
+    postprocess() takes as it is.  params: DenoiseParams; None takes default_denoise_params() with the sigma
+    of an absent guide switched off."""
+    accum = np.ascontiguousarray(accum, np.float32)
+    h, w, _ = accum.shape
+    if params is None:
+        params = default_denoise_params()
+        for k, g in enumerate((guide0, guide1)):
+            if g is None:
+                params.sigma_guide[k] = 0.0
+    fp = C.POINTER(C.c_float)
+    guides = []
+    for g in (guide0, guide1):
+        if g is not None:
+            g = np.ascontiguousarray(g, np.float32)
+            assert g.shape == accum.shape
+        guides.append(g)
+    out = np.zeros((h, w, 4), np.float32)
+    buf = AccumulationBuffer(w, h, 0, accum.ctypes.data_as(fp))
+    _check(lib().rt_denoise(device, C.byref(buf), *[g.ctypes.data_as(fp) if g is not None else None for g in guides],
+                            C.byref(params), out.ctypes.data_as(fp)))
     return out
 
 

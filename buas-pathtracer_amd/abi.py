@@ -187,6 +187,11 @@ class SceneConfig(C.Structure):       # rt_scene_config (per-scene schedule and 
                 ("reserved", C.c_int32 * 3)]
 
 
+class DenoiseParams(C.Structure):     # rt_denoise_params (the denoise stage)
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_guide", C.c_float * 2),
+                ("firefly_clamp", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("node_count", C.c_uint32), ("leaf_count", C.c_uint32), ("max_depth", C.c_uint32),
                 ("max_leaf_size", C.c_uint32)]
@@ -241,6 +246,15 @@ ABI_FUNCTIONS = {
     "rt_postprocess_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, P(PostSettings), C.c_uint32,
                                         C.c_void_p, C.c_void_p]),
     "rt_postprocess": (C.c_int, [C.c_int, P(AccumulationBuffer), P(PostSettings), C.c_uint32, P(C.c_uint32)]),
+    "rt_denoise_default_params": (C.c_int, [P(DenoiseParams)]),
+    "rt_denoise_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rt_denoise_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                    P(DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise": (C.c_int, [C.c_int, P(AccumulationBuffer), P(C.c_float), P(C.c_float), P(DenoiseParams),
+                             P(C.c_float)]),
+    "rt_render_picture_denoised": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet),
+                                             C.c_uint32, C.c_uint32, C.c_uint32, P(PostSettings), P(DenoiseParams),
+                                             C.c_uint32, P(C.c_uint32), P(Stats)]),
 }
 
 HOST_FUNCTIONS = {

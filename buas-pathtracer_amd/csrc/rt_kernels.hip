@@ -5835,3 +5835,10 @@ int rt_debug_intersect(rt_scene* s, uint32_t count, const rt_ray_query* rays, in
 }
 
 }  // extern "C"
+
+// Host helpers for the library's other translation units (rt_internal.h): rt_last_error's message, the
+// device binding and a scene's device.  Not part of the C ABI.
+#include "rt_internal.h"
+void rt_internal_set_error(const char* message) { set_error(message); }
+int rt_internal_bind_device(int device) { return bind_device(device); }
+int rt_internal_scene_device(const rt_scene* scene) { return scene->device; }

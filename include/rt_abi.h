@@ -432,6 +432,56 @@ int rt_postprocess_device(int device, const float* d_pixels, uint32_t w, uint32_
 int rt_postprocess(int device, const rt_accumulation_buffer* accum, const rt_post_settings* post,
                    uint32_t total_frame_index, uint32_t* out_bgra);
 
+/* The denoise stage: an edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch, HPG 2010)
+ * between an accumulation buffer and the output pass.  Beyond the reference, which has no denoiser: an
+ * opt-in that no other entry calls.  DESIGN.md ("The denoise stage") defines it operation by operation;
+ * the device matches the plain-C restatement tests/ref_denoise/ref_denoise.c bit for bit.  In short:
+ *   - beauty and the (up to two, either may be NULL) guide buffers are w*h float4 accumulation buffers
+ *     (sum w*rgb, sum w), resolved per pixel as the output pass resolves: xyz / w when w > 0.001f;
+ *   - a pixel is valid when its beauty weight is > 0.001f, its resolved colour is finite, and every guide
+ *     that is present has a weight > 0.001f and a finite resolved value there.  Invalid pixels come out
+ *     as they went in (all four floats: the output pass still shows NaN as cyan and a negative weight as
+ *     magenta) and contribute to no neighbour;
+ *   - the resolved colour is clamped to [0, firefly_clamp] per channel (no upper clamp when 0);
+ *   - iteration i of `iterations` runs the 5x5 B3-spline kernel {1/16, 1/4, 3/8, 1/4, 1/16}^2 with holes
+ *     at step 2^i, each tap weighted by expf(-e), e = (l(p) - l(q))^2 / (sigma_color 2^-i)^2
+ *     + sum_k |g_k(p) - g_k(q)|^2 / sigma_guide[k]^2, where l = 1 - expf(-luminance) of the current colour
+ *     (Rec. 709 weights) and g_k the resolved guide values; taps outside the image or invalid are skipped
+ *     and the weights renormalised;
+ *   - a valid pixel comes out as {r, g, b, 1.0f}, so rt_postprocess_device takes the buffer as it is.
+ * rt_denoise_default_params: 3 iterations, sigma_color 1.0, sigma_guide {0.1, 0.05} (guide 0 = a Normals
+ * frame, guide 1 = a Distances frame, integrators 4 and 5), firefly_clamp 10. */
+typedef struct rt_denoise_params {
+    int32_t iterations;        /* 1..8 */
+    float   sigma_color;       /* tonemapped-luminance term, halved per iteration; 0 = off */
+    float   sigma_guide[2];    /* per guide buffer; 0 = term off */
+    float   firefly_clamp;     /* per-channel clamp of the resolved radiance before filtering; 0 = none */
+    int32_t reserved[3];
+} rt_denoise_params;
+int    rt_denoise_default_params(rt_denoise_params* out);                 /* no device needed */
+size_t rt_denoise_workspace_bytes(uint32_t w, uint32_t h);                /* 64 bytes per pixel; no device needed */
+/* Device pointers on `device` (w*h float4 each); d_out may equal d_beauty.  d_workspace holds
+ * rt_denoise_workspace_bytes(w, h) bytes; with NULL the call allocates and frees its own.  `hip_stream` may
+ * be NULL; returns after the filter has completed.  RT_ERROR_INVALID, naming the field, for a NULL beauty,
+ * parameter or output pointer, w or h of 0, iterations outside 1..8, a negative or non-finite sigma or
+ * clamp, and a non-zero sigma_guide[k] whose guide is NULL: all checked before the device is touched. */
+int rt_denoise_device(int device, const float* d_beauty, const float* d_guide0, const float* d_guide1,
+                      uint32_t w, uint32_t h, const rt_denoise_params* p, void* d_workspace,
+                      float* d_out, void* hip_stream);
+/* Same, from and to host memory (beauty->pixels, guide0, guide1 in; out_pixels w*h float4 out).
+ * RT_ERROR_NO_DEVICE without a GPU (after the argument checks). */
+int rt_denoise(int device, const rt_accumulation_buffer* beauty, const float* guide0, const float* guide1,
+               const rt_denoise_params* p, float* out_pixels);
+/* rt_render_picture with the denoise stage, written on the public entries: fresh device buffers; the beauty
+ * frame as rt_render_picture renders it (the caller's settings, frame_count 0); a Normals and a Distances
+ * frame of guide_spp samples per pixel (0: the beauty frame's count) with the same camera, filter, tiles
+ * and total_frame_index; rt_denoise_device with guide 0 = normals and guide 1 = distances;
+ * rt_postprocess_device with the dither texture of total_frame_index + 1.  `stats` is the beauty frame's. */
+int rt_render_picture_denoised(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                               const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                               uint32_t w, uint32_t h, const rt_post_settings* post, const rt_denoise_params* p,
+                               uint32_t guide_spp, uint32_t* out_bgra, rt_stats* stats);
+
 /* The reference's top-down BVH builders on the device (RT/bvh.cpp:222-326 with
  * partition_midpoint :53-61, partition_sah_binned :138-213 or the full SAH sweep
  * partition_objects_sah / evaluate_sah :63-131, the partition of :26-51): one launch per
