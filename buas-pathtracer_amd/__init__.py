@@ -22,14 +22,15 @@ import numpy as np
 
 from . import abi
 from .abi import (V3, v3, M4x4Inv, Material, Camera, Settings, FilterCache, PostSettings, TileSet, Stats,
-                  AccumulationBuffer, RayQuery, HitRecord, BvhInfo, DenoiseParams)
+                  AccumulationBuffer, RayQuery, HitRecord, BvhInfo, DenoiseParams, DenoiseFeaturesParams)
 
 __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settings", "load_reconstruction_kernel",
            "translate", "scale", "rotate_x", "rotate_y", "rotate_z", "identity", "aim_camera", "aim_camera_at",
            "recompute_camera", "resolve_bgra8", "postprocess", "write_bitmap", "lib", "abi", "v3", "PI_32", "DEG_TO_RAD",
            "set_splat_mode", "splat_mode", "take_picture", "read_bitmap", "integrator_name", "find_integrator",
            "integrator_supported", "scene_integrator_supported", "DenoiseParams", "default_denoise_params", "denoise",
-           "denoise_workspace_bytes"]
+           "denoise_workspace_bytes", "DenoiseFeaturesParams", "default_denoise_features_params", "denoise_features",
+           "denoise_features_workspace_bytes"]
 
 PI_32 = 3.14159265359
 DEG_TO_RAD = 6.28318530717 / 360.0
@@ -351,6 +352,47 @@ class DeviceScene:
             out.append(self.render(camera, st, filter_cache, w, h, total_frame_index=total_frame_index, tile=tile)[0])
         return out[0], out[1]
 
+    def render_feature(self, camera, settings, filter_cache, w, h, feature, accum=None, frame_count=0,
+                       total_frame_index=0, tile=64, shard_index=0, shard_count=1):
+        """rt_render_feature: adds one feature frame (abi.RT_FEATURE_NORMAL, _DISTANCE or _ALBEDO: what the pixel
+        shows at the end of its specular prefix) into `accum` (float32 [h,w,4], host) -> (accum, stats)."""
+        if accum is None:
+            accum = np.zeros((h, w, 4), np.float32)
+        assert accum.dtype == np.float32 and accum.flags.c_contiguous and accum.shape == (h, w, 4)
+        buf = AccumulationBuffer(w, h, frame_count, accum.ctypes.data_as(C.POINTER(C.c_float)))
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        _check(lib().rt_render_feature(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache), C.byref(tiles),
+                                       total_frame_index, int(feature), C.byref(buf), C.byref(stats)))
+        return accum, stats
+
+    def render_feature_device(self, camera, settings, filter_cache, w, h, feature, d_pixels, stream=None,
+                              frame_count=0, total_frame_index=0, tile=64, shard_index=0, shard_count=1):
+        """rt_render_feature_device into a device pointer (e.g. torch tensor .data_ptr())."""
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        _check(lib().rt_render_feature_device(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                              C.byref(tiles), total_frame_index, w, h, frame_count, int(feature),
+                                              C.c_void_p(d_pixels), C.c_void_p(stream) if stream else None,
+                                              C.byref(stats)))
+        return stats
+
+    def render_picture_features_denoised(self, camera, settings, filter_cache, w, h, post, params=None, guide_spp=0,
+                                         total_frame_index=0, tile=64, shard_index=0, shard_count=1):
+        """rt_render_picture_features_denoised: rt_render_picture with the denoise stage guided by the three
+        feature frames of `guide_spp` samples per pixel (0: the beauty frame's count), demodulated by the
+        albedo frame -> (BGRA8 (h, w) u32, the beauty frame's stats)."""
+        if params is None:
+            params = default_denoise_features_params()
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        out = np.zeros((h, w), np.uint32)
+        stats = Stats()
+        _check(lib().rt_render_picture_features_denoised(self._h, C.byref(camera), C.byref(settings),
+                                                         C.byref(filter_cache), C.byref(tiles), total_frame_index, w, h,
+                                                         C.byref(post), C.byref(params), guide_spp,
+                                                         out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(stats)))
+        return out, stats
+
     def render_picture_denoised(self, camera, settings, filter_cache, w, h, post, params=None, guide_spp=0,
                                 total_frame_index=0, tile=64, shard_index=0, shard_count=1):
         """rt_render_picture_denoised: the frame of rt_render_picture with the denoise stage between the
@@ -453,6 +495,47 @@ def denoise(accum, guide0=None, guide1=None, params=None, device=0):
     buf = AccumulationBuffer(w, h, 0, accum.ctypes.data_as(fp))
     _check(lib().rt_denoise(device, C.byref(buf), *[g.ctypes.data_as(fp) if g is not None else None for g in guides],
                             C.byref(params), out.ctypes.data_as(fp)))
+    return out
+
+
+def default_denoise_features_params():
+    """rt_denoise_features_default_params (no device needed) -> DenoiseFeaturesParams."""
+    p = DenoiseFeaturesParams()
+    _check(lib().rt_denoise_features_default_params(C.byref(p)))
+    return p
+
+
+def denoise_features_workspace_bytes(w, h):
+    """rt_denoise_features_workspace_bytes (no device needed): 80 bytes per pixel."""
+    return int(lib().rt_denoise_features_workspace_bytes(w, h))
+
+
+def denoise_features(accum, normal=None, distance=None, albedo=None, params=None, device=0):
+    """The denoise stage with feature frames on the GPU (rt_denoise_features): host float4 accumulation buffers
+    (h, w, 4) in -- the beauty frame and DeviceScene.render_feature's NORMAL, DISTANCE and ALBEDO frames -- and
+    the filtered buffer out.  params: DenoiseFeaturesParams; None takes default_denoise_features_params() with
+    the terms of an absent frame switched off."""
+    accum = np.ascontiguousarray(accum, np.float32)
+    h, w, _ = accum.shape
+    if params is None:
+        params = default_denoise_features_params()
+        for k, g in enumerate((normal, distance)):
+            if g is None:
+                params.base.sigma_guide[k] = 0.0
+        if albedo is None:
+            params.sigma_albedo, params.demodulate = 0.0, 0
+    fp = C.POINTER(C.c_float)
+    frames = []
+    for g in (normal, distance, albedo):
+        if g is not None:
+            g = np.ascontiguousarray(g, np.float32)
+            assert g.shape == accum.shape
+        frames.append(g)
+    out = np.zeros((h, w, 4), np.float32)
+    buf = AccumulationBuffer(w, h, 0, accum.ctypes.data_as(fp))
+    _check(lib().rt_denoise_features(device, C.byref(buf),
+                                     *[g.ctypes.data_as(fp) if g is not None else None for g in frames],
+                                     C.byref(params), out.ctypes.data_as(fp)))
     return out
 
 

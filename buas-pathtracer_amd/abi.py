@@ -192,6 +192,15 @@ class DenoiseParams(C.Structure):     # rt_denoise_params (the denoise stage)
                 ("firefly_clamp", C.c_float), ("reserved", C.c_int32 * 3)]
 
 
+RT_FEATURE_NORMAL, RT_FEATURE_DISTANCE, RT_FEATURE_ALBEDO = range(3)   # rt_feature (feature frames)
+RT_FEATURE_COUNT = 3
+
+
+class DenoiseFeaturesParams(C.Structure):     # rt_denoise_features_params (the denoise stage with feature frames)
+    _fields_ = [("base", DenoiseParams), ("sigma_albedo", C.c_float), ("demodulate", C.c_int32),
+                ("albedo_floor", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("node_count", C.c_uint32), ("leaf_count", C.c_uint32), ("max_depth", C.c_uint32),
                 ("max_leaf_size", C.c_uint32)]
@@ -255,6 +264,20 @@ ABI_FUNCTIONS = {
     "rt_render_picture_denoised": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet),
                                              C.c_uint32, C.c_uint32, C.c_uint32, P(PostSettings), P(DenoiseParams),
                                              C.c_uint32, P(C.c_uint32), P(Stats)]),
+    "rt_render_feature_device": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
+                                           C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+                                           P(Stats)]),
+    "rt_render_feature": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
+                                    C.c_int, P(AccumulationBuffer), P(Stats)]),
+    "rt_denoise_features_default_params": (C.c_int, [P(DenoiseFeaturesParams)]),
+    "rt_denoise_features_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rt_denoise_features_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                             C.c_uint32, P(DenoiseFeaturesParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise_features": (C.c_int, [C.c_int, P(AccumulationBuffer), P(C.c_float), P(C.c_float), P(C.c_float),
+                                      P(DenoiseFeaturesParams), P(C.c_float)]),
+    "rt_render_picture_features_denoised": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet),
+                                                      C.c_uint32, C.c_uint32, C.c_uint32, P(PostSettings),
+                                                      P(DenoiseFeaturesParams), C.c_uint32, P(C.c_uint32), P(Stats)]),
 }
 
 HOST_FUNCTIONS = {

@@ -2334,9 +2334,86 @@ RT_D bool shade_bounce_gt(const DevScene& sc, const rt_settings& st, const Hit& 
     return bounce >= st.max_bounce_count;
 }
 
+// The feature frames (rt_render_feature_device): k_shade's INTEG past rt_integrator, one per rt_feature.
+constexpr int INTEG_FEATURE0 = 16;
+static_assert(INTEG_FEATURE0 >= RT_INTEGRATOR_COUNT, "the feature modes lie outside rt_integrator");
+
+// One bounce of the feature walk ("Feature frames"): shade_bounce above cut off at its first
+// non-specular vertex.  Inside / outside, mi / mt and the material stack at pool.mstack are that function's,
+// as are the Fresnel test, its S_Reflectance draw, the rough reflection's random_in_unit_sphere and the
+// offsets of the reflected and the refracted ray; no throughput is carried (no Beer term), and nothing else
+// is drawn.  T is the distance accumulated along the prefix, a plain f32 sum in bounce order: the single-chain
+// modes leave Pool::prev_n.x free (0 from k_generate), and it travels there.  st.max_bounce_count is the
+// host's max(max_bounce_count, 1).  The walk ends on an emitter, on the diffuse branch and at the bound; what
+// is recorded there: 0.5*(1 + N) with N as hit_geometry returns it, 1 - saturate(T/15), or the diffuse vertex's
+// evaluate_material (1 where the walk ended otherwise); on a miss the sky of the last direction (albedo 1).
+// No shadow ray.  Returns true when the walk ends.
+template <int FEATURE>
+RT_D bool shade_bounce_feat(const DevScene& sc, const rt_settings& st, const SamplerState& ss, const Pool& pool,
+                            uint32_t slot, const Hit& h, V3& ro, V3& rd, V3& total, float& T, uint32_t& bounce,
+                            int32_t& at, Rng& rng) {
+    if (h.code == RT_HIT_MISS) {
+        total = FEATURE == RT_FEATURE_ALBEDO ? v3s(1.0f) : sample_sky(sc, rd);
+        return true;
+    }
+    V3 I, N;
+    uint32_t surf_id;
+    Ray ray; ray.o = ro; ray.d = rd;
+    hit_geometry(sc, ray, h, I, N, surf_id);
+    T = T + h.t;
+    if (FEATURE == RT_FEATURE_NORMAL) total = smul(0.5f, add(v3s(1.0f), N));
+    if (FEATURE == RT_FEATURE_DISTANCE) total = v3s(1.0f - clampf_(T / 15.0f, 0.0f, 1.0f));
+    if (FEATURE == RT_FEATURE_ALBEDO) total = v3s(1.0f);
+    float cos_i = -dot(rd, N);
+    const bool inside = (cos_i < 0.0f);
+    uint32_t mi_id, mt_id;
+    if (inside) {
+        mi_id = surf_id;
+        const int32_t lv = at - 1 > 0 ? at - 1 : 0;
+        mt_id = lv ? pool.mstack[(size_t)lv*pool.n + slot] : sc.air_id;         // level 0 = air
+        cos_i = -cos_i;
+        N = neg(N);
+    } else {
+        mi_id = at ? pool.mstack[(size_t)at*pool.n + slot] : sc.air_id;
+        mt_id = surf_id;
+    }
+    const rt_material mi = sc.materials[mi_id];
+    const rt_material mt = sc.materials[mt_id];
+    if (mt.flags & RT_MATERIAL_EMISSIVE) return true;
+    const float eta_i = mi.ior, eta_t = mt.ior;
+    const float eta = eta_i / eta_t;
+    float cos_t;
+    float refl = fresnel_dielectric(cos_i, eta_i, eta_t, eta, cos_t);
+    const float reflect_test = sample_1d(sc, ss, rng, S_Reflectance, bounce);
+    refl = lerpf_(refl, 1.0f, mt.metallic);
+    if (reflect_test < refl) {                                              // reflect
+        V3 nd = reflect(rd, N);
+        if (mt.roughness > 0.0f) {
+            V3 rs = random_in_unit_sphere(rng);
+            nd = normalize(add(smul(1.0f + EPSILON, nd), smul(mt.roughness, rs)));
+        }
+        ro = add(I, smul(EPSILON, nd)); rd = nd;
+    } else if (mt.is_participating_medium) {                               // refract
+        if (inside) {
+            if (at > 0) --at;
+        } else if (at < 63) {
+            ++at;
+            pool.mstack[(size_t)at*pool.n + slot] = (uint16_t)mt_id;       // moved with the path (k_shade)
+        }
+        V3 fd = add(smul(eta, rd), muls(N, (eta*cos_i - cos_t)));
+        ro = add(I, muls(fd, EPSILON)); rd = fd;
+    } else {                                                                // the diffuse branch: the walk's end
+        if (FEATURE == RT_FEATURE_ALBEDO) total = evaluate_material(mt, I);
+        return true;
+    }
+    ++bounce;
+    return bounce >= st.max_bounce_count;
+}
+
 // ENV: rt_set_env_sampling on, the scene has an environment map and NEE is on
 // INTEG: the rt_integrator the bounce is one of (shade_bounce, or shade_bounce_gt for the others, which
-// queue no shadow ray: their instantiations drop the NEE staging below)
+// queue no shadow ray: their instantiations drop the NEE staging below), or INTEG_FEATURE0 + an rt_feature
+// (shade_bounce_feat: no shadow ray either)
 //
 // RAMP (r09, the Advanced integrator): the instantiation the iterations near the frame's end carry.  While
 // Counters::ramp is clear it is the kernel above.  In a ramp iteration (every sample claimed, the drain not
@@ -2451,6 +2528,8 @@ __global__ void __launch_bounds__(BLOCK) RT_SHADE_ATTR k_shade(DevScene sc_g, rt
         if constexpr (INTEG == RT_INTEGRATOR_ADVANCED)
             done = shade_bounce<ENV>(sc, st, ss, pool, src, h, ro, rd, thr, total, prev_pdf, bounce, is_spec, at, rng,
                                      cast_shadow, sh_o, sh_d, sh_c, sh_t, sh_light);
+        else if constexpr (INTEG >= INTEG_FEATURE0)         // prev_pdf carries the walk's accumulated distance
+            done = shade_bounce_feat<INTEG - INTEG_FEATURE0>(sc, st, ss, pool, src, h, ro, rd, total, prev_pdf, bounce, at, rng);
         else
             done = shade_bounce_gt<INTEG>(sc, st, h, ro, rd, thr, total, bounce, rng);
         // The survivor's state that the two prologues below do not change goes out now, so the
@@ -4425,6 +4504,12 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
             shade_gt(std::integral_constant<int, RT_INTEGRATOR_NORMALS>{});
         } else if (integ == RT_INTEGRATOR_DISTANCES) {
             shade_gt(std::integral_constant<int, RT_INTEGRATOR_DISTANCES>{});
+        } else if (integ == INTEG_FEATURE0 + RT_FEATURE_NORMAL) {       // shade_bounce_feat<FEATURE>
+            shade_gt(std::integral_constant<int, INTEG_FEATURE0 + RT_FEATURE_NORMAL>{});
+        } else if (integ == INTEG_FEATURE0 + RT_FEATURE_DISTANCE) {
+            shade_gt(std::integral_constant<int, INTEG_FEATURE0 + RT_FEATURE_DISTANCE>{});
+        } else if (integ == INTEG_FEATURE0 + RT_FEATURE_ALBEDO) {
+            shade_gt(std::integral_constant<int, INTEG_FEATURE0 + RT_FEATURE_ALBEDO>{});
         } else if (ramp_shade && r.near) {
             // near the frame's end: the ramp-capable instantiation (one launch: it is the standard kernel
             // while Counters::ramp is clear, so any mix with the launches above is safe)
@@ -5338,14 +5423,27 @@ int rt_postprocess(int device, const rt_accumulation_buffer* accum, const rt_pos
     return err;
 }
 
-int rt_render_device(rt_scene* s, const rt_camera* camera, const rt_settings* st,
-                     const rt_filter_cache* filter, const rt_tile_set* tiles,
-                     uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
-                     float* d_pixels, void* hip_stream, rt_stats* stats) {
+// rt_render_device (feature < 0) and rt_render_feature_device (an rt_feature): one frame into d_pixels.
+// A feature frame ignores rt_settings::integrator and runs k_shade's mode INTEG_FEATURE0 + feature with a
+// bound of max(max_bounce_count, 1), as the first-hit integrators trace their camera ray whatever the count.
+static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_settings* st,
+                               const rt_filter_cache* filter, const rt_tile_set* tiles,
+                               uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
+                               int feature, float* d_pixels, void* hip_stream, rt_stats* stats) {
     if (!s || !camera || !tiles || !d_pixels || !w || !h) { set_error("null argument"); return RT_ERROR_INVALID; }
+    rt_settings feat_st;
+    if (feature >= 0 && st) {
+        feat_st = *st;
+        feat_st.integrator = RT_INTEGRATOR_ADVANCED;
+        st = &feat_st;
+    }
     int err = check_inputs(s, st, filter);
     if (err) return err;
-    const rt_settings dev_st = device_settings(*st);
+    rt_settings dev_st = device_settings(*st);
+    if (feature >= 0) {
+        dev_st.integrator = INTEG_FEATURE0 + feature;
+        dev_st.max_bounce_count = std::max<uint32_t>(dev_st.max_bounce_count, 1u);
+    }
     st = &dev_st;
     if (!tiles->tile_w || !tiles->tile_h || !tiles->shard_count || tiles->shard_index >= tiles->shard_count) {
         set_error("bad tile set"); return RT_ERROR_INVALID;
@@ -5631,6 +5729,48 @@ int rt_render_device(rt_scene* s, const rt_camera* camera, const rt_settings* st
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     return RT_OK;
+}
+
+int rt_render_device(rt_scene* s, const rt_camera* camera, const rt_settings* st,
+                     const rt_filter_cache* filter, const rt_tile_set* tiles,
+                     uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
+                     float* d_pixels, void* hip_stream, rt_stats* stats) {
+    return render_frame_device(s, camera, st, filter, tiles, total_frame_index, w, h, frame_count, -1, d_pixels,
+                               hip_stream, stats);
+}
+
+static int check_feature(const char* entry, int feature) {
+    if (feature >= 0 && feature < RT_FEATURE_COUNT) return RT_OK;
+    set_error(std::string(entry) + ": feature " + std::to_string(feature) + " is no rt_feature (0 NORMAL, 1 DISTANCE, 2 ALBEDO)");
+    return RT_ERROR_INVALID;
+}
+
+int rt_render_feature_device(rt_scene* s, const rt_camera* camera, const rt_settings* st,
+                             const rt_filter_cache* filter, const rt_tile_set* tiles,
+                             uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
+                             int feature, float* d_pixels, void* hip_stream, rt_stats* stats) {
+    int err = check_feature("rt_render_feature_device", feature);
+    if (err) return err;
+    return render_frame_device(s, camera, st, filter, tiles, total_frame_index, w, h, frame_count, feature, d_pixels,
+                               hip_stream, stats);
+}
+
+int rt_render_feature(rt_scene* s, const rt_camera* camera, const rt_settings* st, const rt_filter_cache* filter,
+                      const rt_tile_set* tiles, uint32_t total_frame_index, int feature,
+                      rt_accumulation_buffer* accum, rt_stats* stats) {
+    int err = check_feature("rt_render_feature", feature);
+    if (err) return err;
+    if (!s || !accum || !accum->pixels) { set_error("null argument"); return RT_ERROR_INVALID; }
+    HIP_OK(hipSetDevice(s->device));
+    size_t bytes = (size_t)accum->w*accum->h*4*sizeof(float);
+    float* d = nullptr;
+    HIP_OK(hipMalloc(&d, bytes));
+    if (hipMemcpy(d, accum->pixels, bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("copy in"); err = RT_ERROR_DEVICE; }
+    if (!err) err = rt_render_feature_device(s, camera, st, filter, tiles, total_frame_index, accum->w, accum->h,
+                                             accum->frame_count, feature, d, nullptr, stats);
+    if (!err && hipMemcpy(accum->pixels, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) { set_error("copy out"); err = RT_ERROR_DEVICE; }
+    (void)hipFree(d);
+    return err;
 }
 
 int rt_render(rt_scene* s, const rt_camera* camera, const rt_settings* st, const rt_filter_cache* filter,

@@ -482,6 +482,71 @@ int rt_render_picture_denoised(rt_scene* scene, const rt_camera* camera, const r
                                uint32_t w, uint32_t h, const rt_post_settings* post, const rt_denoise_params* p,
                                uint32_t guide_spp, uint32_t* out_bgra, rt_stats* stats);
 
+/* Feature frames: what a pixel shows at the end of its specular prefix.  Beyond the reference; an opt-in
+ * beside the integrators (rt_settings::integrator is ignored, the integrator table keeps its six rows).
+ * The sample and its camera ray are the beauty frame's (the same key, the same sampler draws, the same
+ * vignette).  The walk is the Advanced integrator cut off at its first non-specular vertex: at each hit,
+ * inside / outside and the material stack as that integrator; T += t; the walk ends when the material
+ * entered is emissive, when the Fresnel test takes the diffuse branch of a material that is no
+ * participating medium, or at hit number max(max_bounce_count, 1); otherwise it reflects or refracts as
+ * the integrator does (its Sample_Reflectance and random_in_unit_sphere draws, no others) and goes on.
+ *   RT_FEATURE_NORMAL    0.5*(1 + N), N as the intersection returns it (integrator 4's value)
+ *   RT_FEATURE_DISTANCE  1 - saturate(T/15) as a grey (integrator 5's value, of the accumulated distance)
+ *   RT_FEATURE_ALBEDO    evaluate_material at the diffuse vertex (checkers included); (1, 1, 1) on an
+ *                        emitter, at the bound on a specular vertex, and on a miss
+ * On a miss NORMAL and DISTANCE are the sky of the last direction.  No NEE, no shadow ray, no roulette:
+ * rt_stats::shadow_rays is 0 and closest_hit_rays - samples counts the specular bounces followed.  With
+ * max_bounce_count <= 1 the NORMAL and DISTANCE frames are integrator 4's and 5's, bit for bit.
+ * DESIGN.md ("Feature frames") defines the walk operation by operation; the device matches the plain-C
+ * restatement tests/ref_features/ref_features.c bit for bit in the exact splat mode. */
+enum rt_feature { RT_FEATURE_NORMAL = 0, RT_FEATURE_DISTANCE = 1, RT_FEATURE_ALBEDO = 2, RT_FEATURE_COUNT = 3 };
+/* Arguments and accumulation as rt_render_device.  A `feature` outside rt_feature is RT_ERROR_INVALID,
+ * named, before the device is touched. */
+int rt_render_feature_device(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                             const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                             uint32_t w, uint32_t h, uint32_t frame_count, int feature, float* d_pixels,
+                             void* hip_stream, rt_stats* stats);
+/* Same, into host memory, as rt_render. */
+int rt_render_feature(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                      const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                      int feature, rt_accumulation_buffer* accum, rt_stats* stats);
+
+/* The denoise stage with feature frames: rt_denoise_device's filter (guide 0 = a NORMAL frame, guide 1 = a
+ * DISTANCE frame) with an albedo frame, which
+ *   - resolves as the guides do and, when present, takes part in the validity rule like a guide;
+ *   - with `demodulate`, divides the clamped colour per channel by a = max(albedo, albedo_floor) before
+ *     the first iteration (l is taken of the demodulated colour) and multiplies it back after the last;
+ *   - with sigma_albedo > 0, adds |albedo(p) - albedo(q)|^2 / sigma_albedo^2 to a tap's e after the two
+ *     guide terms.
+ * With the albedo NULL, demodulate 0 and sigma_albedo 0 the output is rt_denoise_device's, bit for bit.
+ * The workspace is 80 bytes per pixel.  Refusals as rt_denoise_device, and by name: demodulate or
+ * sigma_albedo > 0 with a NULL albedo, a negative or non-finite sigma_albedo, demodulate outside 0 / 1,
+ * and with demodulate an albedo_floor that is not finite and > 0. */
+typedef struct rt_denoise_features_params {
+    rt_denoise_params base;   /* guide 0 = NORMAL, guide 1 = DISTANCE */
+    float   sigma_albedo;     /* edge-stopping term on the resolved albedo; 0 = off */
+    int32_t demodulate;       /* 0 / 1 */
+    float   albedo_floor;     /* > 0 and finite when demodulate */
+    int32_t reserved[5];
+} rt_denoise_features_params;
+int    rt_denoise_features_default_params(rt_denoise_features_params* out);      /* no device needed */
+size_t rt_denoise_features_workspace_bytes(uint32_t w, uint32_t h);              /* 80 bytes per pixel; no device needed */
+int rt_denoise_features_device(int device, const float* d_beauty, const float* d_normal, const float* d_distance,
+                               const float* d_albedo, uint32_t w, uint32_t h, const rt_denoise_features_params* p,
+                               void* d_workspace, float* d_out, void* hip_stream);
+/* Same, from and to host memory.  RT_ERROR_NO_DEVICE without a GPU (after the argument checks). */
+int rt_denoise_features(int device, const rt_accumulation_buffer* beauty, const float* normal, const float* distance,
+                        const float* albedo, const rt_denoise_features_params* p, float* out_pixels);
+/* rt_render_picture_denoised with feature frames, written on the public entries: the beauty frame; a
+ * NORMAL, a DISTANCE and an ALBEDO frame of guide_spp samples per pixel (0: the beauty frame's count) with
+ * the same camera, filter, tiles, total_frame_index and max_bounce_count; rt_denoise_features_device;
+ * rt_postprocess_device with the dither texture of total_frame_index + 1.  `stats` is the beauty frame's. */
+int rt_render_picture_features_denoised(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                                        const rt_filter_cache* filter, const rt_tile_set* tiles,
+                                        uint32_t total_frame_index, uint32_t w, uint32_t h,
+                                        const rt_post_settings* post, const rt_denoise_features_params* p,
+                                        uint32_t guide_spp, uint32_t* out_bgra, rt_stats* stats);
+
 /* The reference's top-down BVH builders on the device (RT/bvh.cpp:222-326 with
  * partition_midpoint :53-61, partition_sah_binned :138-213 or the full SAH sweep
  * partition_objects_sah / evaluate_sah :63-131, the partition of :26-51): one launch per
