@@ -377,6 +377,36 @@ class DeviceScene:
                                               C.byref(stats)))
         return stats
 
+    def render_features(self, camera, settings, filter_cache, w, h, accums=None, frame_count=0, total_frame_index=0,
+                        tile=64, shard_index=0, shard_count=1):
+        """rt_render_features: the NORMAL, DISTANCE and ALBEDO frames in one walk, added into `accums` (three
+        float32 [h,w,4] host buffers; fresh ones by default) -> (normal, distance, albedo, stats).  Each buffer
+        is what render_feature adds to it; the stats are the one walk's."""
+        if accums is None:
+            accums = [np.zeros((h, w, 4), np.float32) for _ in range(abi.RT_FEATURE_COUNT)]
+        accums = list(accums)
+        assert len(accums) == abi.RT_FEATURE_COUNT
+        for a in accums:
+            assert a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (h, w, 4)
+        bufs = [AccumulationBuffer(w, h, frame_count, a.ctypes.data_as(C.POINTER(C.c_float))) for a in accums]
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        _check(lib().rt_render_features(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache), C.byref(tiles),
+                                        total_frame_index, C.byref(bufs[0]), C.byref(bufs[1]), C.byref(bufs[2]),
+                                        C.byref(stats)))
+        return accums[0], accums[1], accums[2], stats
+
+    def render_features_device(self, camera, settings, filter_cache, w, h, d_normal, d_distance, d_albedo, stream=None,
+                               frame_count=0, total_frame_index=0, tile=64, shard_index=0, shard_count=1):
+        """rt_render_features_device into three distinct device pointers (e.g. torch tensors' .data_ptr())."""
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        _check(lib().rt_render_features_device(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                               C.byref(tiles), total_frame_index, w, h, frame_count,
+                                               C.c_void_p(d_normal), C.c_void_p(d_distance), C.c_void_p(d_albedo),
+                                               C.c_void_p(stream) if stream else None, C.byref(stats)))
+        return stats
+
     def render_picture_features_denoised(self, camera, settings, filter_cache, w, h, post, params=None, guide_spp=0,
                                          total_frame_index=0, tile=64, shard_index=0, shard_count=1):
         """rt_render_picture_features_denoised: rt_render_picture with the denoise stage guided by the three

@@ -269,6 +269,11 @@ ABI_FUNCTIONS = {
                                            P(Stats)]),
     "rt_render_feature": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
                                     C.c_int, P(AccumulationBuffer), P(Stats)]),
+    "rt_render_features_device": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, P(Stats)]),
+    "rt_render_features": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
+                                     P(AccumulationBuffer), P(AccumulationBuffer), P(AccumulationBuffer), P(Stats)]),
     "rt_denoise_features_default_params": (C.c_int, [P(DenoiseFeaturesParams)]),
     "rt_denoise_features_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
     "rt_denoise_features_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,

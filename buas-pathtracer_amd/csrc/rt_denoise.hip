@@ -535,8 +535,9 @@ int rt_render_picture_features_denoised(rt_scene* s, const rt_camera* camera, co
     rt_settings gst = *st;
     if (guide_spp) gst.samples_per_pixel = guide_spp;
     rt_stats guide_stats;
-    for (int f = 0; f < RT_FEATURE_COUNT && !err; ++f)
-        err = rt_render_feature_device(s, camera, &gst, filter, tiles, total_frame_index, w, h, 0u, f, d_feat[f], nullptr, &guide_stats);
+    // (one walk for the three: the buffers are those of three rt_render_feature_device calls, bit for bit)
+    if (!err) err = rt_render_features_device(s, camera, &gst, filter, tiles, total_frame_index, w, h, 0u, d_feat[RT_FEATURE_NORMAL],
+                                              d_feat[RT_FEATURE_DISTANCE], d_feat[RT_FEATURE_ALBEDO], nullptr, &guide_stats);
     if (!err) err = rt_denoise_features_device(device, d_beauty, d_feat[RT_FEATURE_NORMAL], d_feat[RT_FEATURE_DISTANCE],
                                                d_feat[RT_FEATURE_ALBEDO], w, h, p, d_ws, d_beauty, nullptr);
     // the dither texture of total_frame_index + 1, as rt_render_picture picks it

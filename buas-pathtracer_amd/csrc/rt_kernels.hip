@@ -1305,6 +1305,9 @@ struct Pool {
     float4*  rec_rgbx;   // r, g, b, jitter_x
     float*   rec_jy;     // jitter_y
     uint32_t rec_pass0, rec_ring;
+    // The one-pass feature frame (k_shade's INTEG_FEATURES) keeps one ring per rt_feature at the same index:
+    // feature f's records are rec_rgbx / rec_jy + f*rec_feat.  0 in every other frame.
+    size_t   rec_feat;
 };
 
 // Slot states.  Every per-iteration kernel except the tracers walks the pool in
@@ -1397,6 +1400,9 @@ struct FrameParams {
     float*  samp_jy;                // [spp*P]: jitter_y
     const int32_t* tile_base;       // [tiles]: first tile-list pixel of an owned tile, -1 otherwise
     uint32_t spp;
+    // the one-pass feature frame: the buffers of the features past the first (accum is feature 0's); the
+    // atomic splat adds to them directly
+    float4* accum_feat[RT_FEATURE_COUNT - 1];
 };
 
 // wave-aggregated queue append: one atomic per wavefront
@@ -1584,9 +1590,15 @@ constexpr int EV_SLOTS = 4*NIF;  // iterations in flight per partition in run_fr
 // float atomics into the accumulator when the records do not fit.  Run by k_generate on
 // the finished array k_shade wrote (key: ray_d.w, the sample pass or the list index;
 // p: the tile-list pixel).
-RT_D void splat_sample(const FrameParams& fp, const Pool& pool, V3 L, float vig, float2 j, uint32_t key, uint32_t p) {
+RT_D void splat_sample(const FrameParams& fp, const Pool& pool, V3 L, float vig, float2 j, uint32_t key, uint32_t p,
+                       int feat = 0) {
     {
         V3 r = muls(L, vig);
+        // feat: the rt_feature whose ring (Pool::rec_feat) or buffer takes the sample; a one-pass feature
+        // frame's k_shade names the ones past the first, every other caller the frame's only one
+        float4* const rec_rgbx = feat ? pool.rec_rgbx + (size_t)feat*pool.rec_feat : pool.rec_rgbx;
+        float* const rec_jy = feat ? pool.rec_jy + (size_t)feat*pool.rec_feat : pool.rec_jy;
+        float4* const accum = feat ? fp.accum_feat[feat - 1] : fp.accum;
         if (fp.list_xy) {
             float* o = fp.list_out + 5*(size_t)key;
             o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = j.x; o[4] = j.y;
@@ -1594,8 +1606,8 @@ RT_D void splat_sample(const FrameParams& fp, const Pool& pool, V3 L, float vig,
             // deterministic paths: store the sample; k_resolve_tiles / k_resolve gather it
             const uint32_t rel = key - pool.rec_pass0;
             const size_t rec = (size_t)(rel < pool.rec_ring ? rel : rel % pool.rec_ring)*fp.pixels + p;
-            stnt(&pool.rec_rgbx[rec], make_float4(r.x, r.y, r.z, j.x));     // read again only by the resolve
-            stnt(&pool.rec_jy[rec], j.y);
+            stnt(&rec_rgbx[rec], make_float4(r.x, r.y, r.z, j.x));     // read again only by the resolve
+            stnt(&rec_jy[rec], j.y);
         } else if (fp.cache_size) {
             const uint32_t xy = fp.pix_xy[p];
             const int64_t x = xy & 0xFFFFu, y = xy >> 16;
@@ -1613,7 +1625,7 @@ RT_D void splat_sample(const FrameParams& fp, const Pool& pool, V3 L, float vig,
                 for (int64_t sx = x0; sx < x1; ++sx) {
                     int32_t jx = (int32_t)fabsf(0.5f + kscale*((float)(xm + (sx - x0) - ks) - j.x));
                     float f = fp.lut[jx]*fy;
-                    float* dst = reinterpret_cast<float*>(fp.accum + (size_t)sy*fp.w + sx);
+                    float* dst = reinterpret_cast<float*>(accum + (size_t)sy*fp.w + sx);
                     unsafeAtomicAdd(dst + 0, f*r.x);
                     unsafeAtomicAdd(dst + 1, f*r.y);
                     unsafeAtomicAdd(dst + 2, f*r.z);
@@ -1622,7 +1634,7 @@ RT_D void splat_sample(const FrameParams& fp, const Pool& pool, V3 L, float vig,
             }
         } else {
             const uint32_t xy = fp.pix_xy[p];
-            float* dst = reinterpret_cast<float*>(fp.accum + (size_t)(xy >> 16)*fp.w + (xy & 0xFFFFu));
+            float* dst = reinterpret_cast<float*>(accum + (size_t)(xy >> 16)*fp.w + (xy & 0xFFFFu));
             unsafeAtomicAdd(dst + 0, r.x);
             unsafeAtomicAdd(dst + 1, r.y);
             unsafeAtomicAdd(dst + 2, r.z);
@@ -2337,6 +2349,8 @@ RT_D bool shade_bounce_gt(const DevScene& sc, const rt_settings& st, const Hit& 
 // The feature frames (rt_render_feature_device): k_shade's INTEG past rt_integrator, one per rt_feature.
 constexpr int INTEG_FEATURE0 = 16;
 static_assert(INTEG_FEATURE0 >= RT_INTEGRATOR_COUNT, "the feature modes lie outside rt_integrator");
+// rt_render_features_device: the three feature frames in one walk (shade_bounce_feat<RT_FEATURE_COUNT>)
+constexpr int INTEG_FEATURES = INTEG_FEATURE0 + RT_FEATURE_COUNT;
 
 // One bounce of the feature walk ("Feature frames"): shade_bounce above cut off at its first
 // non-specular vertex.  Inside / outside, mi / mt and the material stack at pool.mstack are that function's,
@@ -2348,12 +2362,20 @@ static_assert(INTEG_FEATURE0 >= RT_INTEGRATOR_COUNT, "the feature modes lie outs
 // is recorded there: 0.5*(1 + N) with N as hit_geometry returns it, 1 - saturate(T/15), or the diffuse vertex's
 // evaluate_material (1 where the walk ended otherwise); on a miss the sky of the last direction (albedo 1).
 // No shadow ray.  Returns true when the walk ends.
+//
+// FEATURE == RT_FEATURE_COUNT (rt_render_features_device, k_shade's INTEG_FEATURES) is the same walk recording
+// all three: none of the values travels with the path (the normal and the distance are overwritten at every
+// hit, the albedo is 1 until the walk's end), so the call that ends the walk knows them all.  `total` is then
+// the NORMAL value and dist / albedo the other two, each the operations of its single-feature form; both are
+// meaningful only when the call returns true.
 template <int FEATURE>
 RT_D bool shade_bounce_feat(const DevScene& sc, const rt_settings& st, const SamplerState& ss, const Pool& pool,
                             uint32_t slot, const Hit& h, V3& ro, V3& rd, V3& total, float& T, uint32_t& bounce,
-                            int32_t& at, Rng& rng) {
+                            int32_t& at, Rng& rng, V3& dist, V3& albedo) {
+    constexpr bool ALL = FEATURE == RT_FEATURE_COUNT;
     if (h.code == RT_HIT_MISS) {
         total = FEATURE == RT_FEATURE_ALBEDO ? v3s(1.0f) : sample_sky(sc, rd);
+        if (ALL) { dist = total; albedo = v3s(1.0f); }
         return true;
     }
     V3 I, N;
@@ -2361,9 +2383,10 @@ RT_D bool shade_bounce_feat(const DevScene& sc, const rt_settings& st, const Sam
     Ray ray; ray.o = ro; ray.d = rd;
     hit_geometry(sc, ray, h, I, N, surf_id);
     T = T + h.t;
-    if (FEATURE == RT_FEATURE_NORMAL) total = smul(0.5f, add(v3s(1.0f), N));
+    if (FEATURE == RT_FEATURE_NORMAL || ALL) total = smul(0.5f, add(v3s(1.0f), N));
     if (FEATURE == RT_FEATURE_DISTANCE) total = v3s(1.0f - clampf_(T / 15.0f, 0.0f, 1.0f));
     if (FEATURE == RT_FEATURE_ALBEDO) total = v3s(1.0f);
+    if (ALL) { dist = v3s(1.0f - clampf_(T / 15.0f, 0.0f, 1.0f)); albedo = v3s(1.0f); }
     float cos_i = -dot(rd, N);
     const bool inside = (cos_i < 0.0f);
     uint32_t mi_id, mt_id;
@@ -2404,6 +2427,7 @@ RT_D bool shade_bounce_feat(const DevScene& sc, const rt_settings& st, const Sam
         ro = add(I, muls(fd, EPSILON)); rd = fd;
     } else {                                                                // the diffuse branch: the walk's end
         if (FEATURE == RT_FEATURE_ALBEDO) total = evaluate_material(mt, I);
+        if (ALL) albedo = evaluate_material(mt, I);
         return true;
     }
     ++bounce;
@@ -2525,11 +2549,13 @@ __global__ void __launch_bounds__(BLOCK) RT_SHADE_ATTR k_shade(DevScene sc_g, rt
         SamplerState ss = {px, py, canonical, st.sampling_strategy};
         Hit h;
         h.t = h4.x; h.code = __float_as_uint(h4.y); h.tri = __float_as_uint(h4.z); h.v = h4.w; h.w = hw;
+        V3 feat_dist = {0, 0, 0}, feat_albedo = {0, 0, 0};          // INTEG_FEATURES: the walk's other two values
         if constexpr (INTEG == RT_INTEGRATOR_ADVANCED)
             done = shade_bounce<ENV>(sc, st, ss, pool, src, h, ro, rd, thr, total, prev_pdf, bounce, is_spec, at, rng,
                                      cast_shadow, sh_o, sh_d, sh_c, sh_t, sh_light);
         else if constexpr (INTEG >= INTEG_FEATURE0)         // prev_pdf carries the walk's accumulated distance
-            done = shade_bounce_feat<INTEG - INTEG_FEATURE0>(sc, st, ss, pool, src, h, ro, rd, total, prev_pdf, bounce, at, rng);
+            done = shade_bounce_feat<INTEG - INTEG_FEATURE0>(sc, st, ss, pool, src, h, ro, rd, total, prev_pdf, bounce, at, rng,
+                                                             feat_dist, feat_albedo);
         else
             done = shade_bounce_gt<INTEG>(sc, st, h, ro, rd, thr, total, bounce, rng);
         // The survivor's state that the two prologues below do not change goes out now, so the
@@ -2562,6 +2588,19 @@ __global__ void __launch_bounds__(BLOCK) RT_SHADE_ATTR k_shade(DevScene sc_g, rt
         }
         const float vig = __uint_as_float(meta.z);
         const uint32_t nflags = pack_flags(bounce, is_spec, (uint32_t)at);
+        if constexpr (INTEG == INTEG_FEATURES) {
+            // The one-pass feature frame.  The NORMAL value takes the finished array below and k_generate's
+            // splat, as every frame's sample does; the DISTANCE and ALBEDO values are splatted here, into
+            // their own rings or buffers (splat_sample's feat), with the jitter k_generate would recompute:
+            // a single-chain path has no NEE term to wait for.  The same records as their single-feature
+            // frames write, so the resolves, run once per ring, give those frames' sums.
+            if (done) {
+                const uint32_t fs = fp.list_xy ? fp.list_s[meta.y] : meta.y;
+                const V2 j = sample_jitter(sc_g, st, fp, meta.x & 0xFFFFu, meta.x >> 16, fs);
+                splat_sample(fp, pool, feat_dist, vig, make_float2(j.x, j.y), meta.y, meta.w, RT_FEATURE_DISTANCE);
+                splat_sample(fp, pool, feat_albedo, vig, make_float2(j.x, j.y), meta.y, meta.w, RT_FEATURE_ALBEDO);
+            }
+        }
         if (cast_shadow) {
             // intersect_shadow_ray (:756): planes and the top level here; only rays that meet
             // a mesh are queued for the next iteration's k_trace.  Nothing else adds to total_color after the
@@ -3828,6 +3867,9 @@ __global__ void __launch_bounds__(256) k_post(const float4* px, uint32_t w, uint
 // so one partition's kernels fill the GPU while another's persistent trace
 // kernel drains its last long rays (the per-launch tail).
 constexpr int MAX_PARTITIONS = 8;
+// rt_scene::d_aux starts with the partials' address tables, one of MAX_PARTITIONS pointers per rt_feature
+// (a frame that is no one-pass feature frame uses the first), in 32-bit words
+constexpr size_t AUX_TABLES = 2*(size_t)MAX_PARTITIONS*RT_FEATURE_COUNT;
 struct Partition {
     Pool pool = {};
     std::vector<void*> pool_allocs;
@@ -3886,6 +3928,7 @@ struct rt_scene {
         const void* aux_partials = nullptr; // d_partials / npx the device pointer table holds
         size_t aux_npx = 0;
         int aux_parts = -1;
+        int aux_feat = 1;                   // the features the table holds (3: a one-pass feature frame's)
     } layout;
     volatile int cancel = 0;
     uint32_t bvh_depth = 0;
@@ -4232,14 +4275,26 @@ struct SplatCfg {
     size_t lds = 0;
     float4* partials = nullptr;         // STREAM: partitions 1.. accumulate here (w*h each)
     const float4* const* part_ptrs = nullptr;   // device array of the partials' addresses
+    // The one-pass feature frame (INTEG_FEATURES) splats RT_FEATURE_COUNT values per sample: feature f's
+    // records lie rec_feat*f past rec / rec_jy, its partials parts*npx*f past `partials` (parts = nparts - 1),
+    // its address table MAX_PARTITIONS*f past part_ptrs, and its destination is fp.accum (f = 0) or
+    // fp.accum_feat[f - 1].  Every other frame has nfeat 1.
+    int nfeat = 1;
+    size_t rec_feat = 0;
 };
 
+// dst: the partition's buffer per feature (one, or the one-pass feature frame's three: the kernel runs once per
+// ring, with the ring's base and its buffer as its arguments)
 void launch_resolve_tiles(const SplatCfg& sp, const FrameParams& fp, const Pool& pool, const Counters* cnt,
-                          float4* dst, hipStream_t q) {
-    switch (sp.ksmax) {
-        case 2:  k_resolve_tiles<2><<<sp.nblocks, TR_THREADS, sp.lds, q>>>(fp, pool, cnt, sp.blocks, dst); break;
-        case 4:  k_resolve_tiles<4><<<sp.nblocks, TR_THREADS, sp.lds, q>>>(fp, pool, cnt, sp.blocks, dst); break;
-        default: k_resolve_tiles<12><<<sp.nblocks, TR_THREADS, sp.lds, q>>>(fp, pool, cnt, sp.blocks, dst); break;
+                          float4* const* dst, hipStream_t q) {
+    for (int f = 0; f < sp.nfeat; ++f) {
+        Pool pf = pool;
+        if (f) { pf.rec_rgbx += (size_t)f*sp.rec_feat; pf.rec_jy += (size_t)f*sp.rec_feat; }
+        switch (sp.ksmax) {
+            case 2:  k_resolve_tiles<2><<<sp.nblocks, TR_THREADS, sp.lds, q>>>(fp, pf, cnt, sp.blocks, dst[f]); break;
+            case 4:  k_resolve_tiles<4><<<sp.nblocks, TR_THREADS, sp.lds, q>>>(fp, pf, cnt, sp.blocks, dst[f]); break;
+            default: k_resolve_tiles<12><<<sp.nblocks, TR_THREADS, sp.lds, q>>>(fp, pf, cnt, sp.blocks, dst[f]); break;
+        }
     }
 }
 
@@ -4281,7 +4336,7 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
     HIP_OK(hipEventRecord(s->start_ev, stream));
     struct Run { hipStream_t stream; uint32_t grid; uint64_t iters, chunks, consumed; int cur; bool live, drain, near;
                  unsigned long long seen_next; int final_buf;
-                 uint64_t chunk_first[NIF]; int chunk_n[NIF]; uint32_t pass0, pass1, ring; float4* dst;
+                 uint64_t chunk_first[NIF]; int chunk_n[NIF]; uint32_t pass0, pass1, ring; float4* dst[RT_FEATURE_COUNT];
                  bool res_ev[EV_SLOTS]; };
     Run run[MAX_PARTITIONS] = {};
     double kms[RT_KERNEL_COUNT] = {};
@@ -4314,6 +4369,7 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
         init.claim_limit = ~0ull;
         Pool& pool = pt.pool;
         pool.rec_rgbx = nullptr; pool.rec_jy = nullptr; pool.rec_pass0 = 0; pool.rec_ring = 1;
+        pool.rec_feat = sp.nfeat > 1 ? sp.rec_feat : 0;
         if (listed) {
             init.next_sample = total*(unsigned long long)k / nparts;
             init.total_samples = total*(unsigned long long)(k + 1) / nparts;
@@ -4334,8 +4390,10 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
                 pool.rec_jy = sp.rec_jy + (size_t)k*sp.ring*fp.pixels;
                 pool.rec_ring = r.ring;
                 init.claim_limit = (unsigned long long)(r.pass0 + r.ring)*fp.pixels;
-                r.dst = k ? sp.partials + (size_t)(k - 1)*npx : fp.accum;
-                if (k) HIP_OK(hipMemsetAsync(r.dst, 0, sizeof(float4)*npx, r.stream));
+                for (int f = 0; f < sp.nfeat; ++f) {
+                    r.dst[f] = k ? sp.partials + ((size_t)f*(nparts - 1) + (k - 1))*npx : f ? fp.accum_feat[f - 1] : fp.accum;
+                    if (k) HIP_OK(hipMemsetAsync(r.dst[f], 0, sizeof(float4)*npx, r.stream));
+                }
             }
         }
         init.start_sample = init.next_sample;
@@ -4510,6 +4568,8 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
             shade_gt(std::integral_constant<int, INTEG_FEATURE0 + RT_FEATURE_DISTANCE>{});
         } else if (integ == INTEG_FEATURE0 + RT_FEATURE_ALBEDO) {
             shade_gt(std::integral_constant<int, INTEG_FEATURE0 + RT_FEATURE_ALBEDO>{});
+        } else if (integ == INTEG_FEATURES) {                           // all three in one walk
+            shade_gt(std::integral_constant<int, INTEG_FEATURES>{});
         } else if (ramp_shade && r.near) {
             // near the frame's end: the ramp-capable instantiation (one launch: it is the standard kernel
             // while Counters::ramp is clear, so any mix with the launches above is safe)
@@ -4647,8 +4707,9 @@ int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long 
         HIP_OK(hipStreamWaitEvent(stream, s->part[k].join, 0));
     }
     if (stream_splat && nparts > 1) {
-        k_combine_partials<<<(uint32_t)std::min<size_t>((npx + 255) / 256, 8192), 256, 0, stream>>>(
-            fp.accum, sp.part_ptrs, nparts - 1, npx);
+        for (int f = 0; f < sp.nfeat; ++f)
+            k_combine_partials<<<(uint32_t)std::min<size_t>((npx + 255) / 256, 8192), 256, 0, stream>>>(
+                f ? fp.accum_feat[f - 1] : fp.accum, sp.part_ptrs + (size_t)f*MAX_PARTITIONS, nparts - 1, npx);
         HIP_OK(hipGetLastError());
     }
     if (stream_splat && ((prof >> RT_KERNEL_RESOLVE) & 1u)) {
@@ -5426,11 +5487,15 @@ int rt_postprocess(int device, const rt_accumulation_buffer* accum, const rt_pos
 // rt_render_device (feature < 0) and rt_render_feature_device (an rt_feature): one frame into d_pixels.
 // A feature frame ignores rt_settings::integrator and runs k_shade's mode INTEG_FEATURE0 + feature with a
 // bound of max(max_bounce_count, 1), as the first-hit integrators trace their camera ray whatever the count.
+// rt_render_features_device (feature == RT_FEATURE_COUNT): the three feature frames in one walk, NORMAL into
+// d_pixels and DISTANCE and ALBEDO into d_more[0..1]; a sample leaves three records, so the splat is planned
+// for three rings (or three whole-frame arrays) and resolved once per ring.
 static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_settings* st,
                                const rt_filter_cache* filter, const rt_tile_set* tiles,
                                uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
-                               int feature, float* d_pixels, void* hip_stream, rt_stats* stats) {
+                               int feature, float* d_pixels, float* const* d_more, void* hip_stream, rt_stats* stats) {
     if (!s || !camera || !tiles || !d_pixels || !w || !h) { set_error("null argument"); return RT_ERROR_INVALID; }
+    const int nfeat = feature == RT_FEATURE_COUNT ? RT_FEATURE_COUNT : 1;
     rt_settings feat_st;
     if (feature >= 0 && st) {
         feat_st = *st;
@@ -5530,6 +5595,7 @@ static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_se
     fp.kernel_size = (int32_t)filter->kernel_size;
     fp.cache_size = (int32_t)filter->cache_size;
     fp.accum = reinterpret_cast<float4*>(d_pixels);
+    for (int f = 1; f < nfeat; ++f) fp.accum_feat[f - 1] = reinterpret_cast<float4*>(d_more[f - 1]);
     const uint32_t spp_all = st->samples_per_pixel;
     const uint32_t pass_lo = by_pass ? (uint32_t)((unsigned long long)spp_all*tiles->shard_index / tiles->shard_count) : 0u;
     const uint32_t pass_hi = by_pass ? (uint32_t)((unsigned long long)spp_all*(tiles->shard_index + 1) / tiles->shard_count)
@@ -5542,7 +5608,10 @@ static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_se
     // reference's order).  The budget is the free memory (plus the records already held)
     // less 16 GB for the partitions' path pools.  EXACT falls back to STREAM over budget or
     // past the filter radius k_resolve_tiles stages (12); STREAM to ATOMIC only if even
-    // one pass per partition does not fit.
+    // one pass per partition does not fit.  A one-pass feature frame keeps nfeat = 3 records per sample
+    // (three rings, or three whole-frame arrays): `rec_b` bytes a sample against the budget, so over it the
+    // exact mode streams and the rings shorten, as for any frame; need_rec stays the records of one feature.
+    const double rec_b = 20.0*nfeat;
     const uint32_t spp = pass_hi - pass_lo;                       // this shard's passes
     const int ks = fp.cache_size ? fp.kernel_size : 0;
     const FrameShape shape = frame_shape(s, st->integrator, total, spp);
@@ -5556,11 +5625,11 @@ static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_se
         sp.pass_lo = pass_lo;
         sp.mode = want_mode;
         need_rec = 0;
-        if (sp.mode == RT_SPLAT_EXACT && (double)total*20.0 > budget) sp.mode = RT_SPLAT_STREAM;
+        if (sp.mode == RT_SPLAT_EXACT && (double)total*rec_b > budget) sp.mode = RT_SPLAT_STREAM;
         // past the radius k_resolve_tiles stages: the exact gather, or atomics for a pass shard (whose
         // records would be placed at pass_lo*P in an array sized for its own passes) or over budget
         if (sp.mode == RT_SPLAT_STREAM && ks > 12)
-            sp.mode = (!by_pass && (double)total*20.0 <= budget) ? RT_SPLAT_EXACT : RT_SPLAT_ATOMIC;
+            sp.mode = (!by_pass && (double)total*rec_b <= budget) ? RT_SPLAT_EXACT : RT_SPLAT_ATOMIC;
         if (sp.mode == RT_SPLAT_STREAM) {
             // a resolve every ~32M samples, and at least four per partition (a small shard, e.g. one
             // rank's eighth of a frame, would otherwise resolve all its passes after its drain); the
@@ -5579,12 +5648,12 @@ static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_se
             sp.ring = (uint32_t)std::min<unsigned long long>(sp.chunk + lag + 2ull, per_part);
             if (s->cfg.splat_ring > 0) sp.ring = (uint32_t)s->cfg.splat_ring;
             sp.chunk = std::min(sp.chunk, sp.ring);                   // the planner needs chunk <= ring
-            while (sp.ring > 1 && 20.0*(double)shape.nparts*sp.ring*fp.pixels > budget) {
+            while (sp.ring > 1 && rec_b*(double)shape.nparts*sp.ring*fp.pixels > budget) {
                 sp.ring = std::max(1u, sp.ring / 2);
                 sp.chunk = std::min(sp.chunk, sp.ring);
             }
             need_rec = (size_t)shape.nparts*sp.ring*fp.pixels;
-            if (20.0*(double)need_rec > budget) { sp.mode = RT_SPLAT_ATOMIC; need_rec = 0; }
+            if (rec_b*(double)need_rec > budget) { sp.mode = RT_SPLAT_ATOMIC; need_rec = 0; }
         }
         if (sp.mode == RT_SPLAT_EXACT) need_rec = (size_t)total;
     };
@@ -5593,23 +5662,23 @@ static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_se
     size_t need_rec = 0;
     const bool fixed_budget = s->cfg.sample_budget_gb >= 0.0;
     plan_splat(fixed_budget ? s->cfg.sample_budget_gb*1e9 : 20.0*(double)s->samp_cap, sp, need_rec);
-    if (!fixed_budget && (sp.mode != want_mode || need_rec > s->samp_cap)) {
+    if (!fixed_budget && (sp.mode != want_mode || need_rec*nfeat > s->samp_cap)) {
         size_t free_b = 0, total_b = 0;
         HIP_OK(hipMemGetInfo(&free_b, &total_b));
         plan_splat((double)free_b + 20.0*(double)s->samp_cap - 16e9, sp, need_rec);
     }
-    if (sp.mode != RT_SPLAT_ATOMIC && s->samp_cap < need_rec) {
+    if (sp.mode != RT_SPLAT_ATOMIC && s->samp_cap < need_rec*nfeat) {
         if (s->d_samp) (void)hipFree(s->d_samp);
         if (s->d_samp_jy) (void)hipFree(s->d_samp_jy);
         s->d_samp = nullptr; s->d_samp_jy = nullptr; s->samp_cap = 0;
-        if (hipMalloc(&s->d_samp, sizeof(float4)*need_rec) != hipSuccess ||
-            hipMalloc(&s->d_samp_jy, sizeof(float)*need_rec) != hipSuccess) {
+        if (hipMalloc(&s->d_samp, sizeof(float4)*need_rec*nfeat) != hipSuccess ||
+            hipMalloc(&s->d_samp_jy, sizeof(float)*need_rec*nfeat) != hipSuccess) {
             (void)hipGetLastError();
             if (s->d_samp) (void)hipFree(s->d_samp);
             s->d_samp = nullptr; s->d_samp_jy = nullptr;
             sp.mode = RT_SPLAT_ATOMIC;                                 // out of memory
         } else {
-            s->samp_cap = need_rec;
+            s->samp_cap = need_rec*nfeat;
         }
     }
     if (sp.mode != RT_SPLAT_ATOMIC) {
@@ -5619,16 +5688,18 @@ static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_se
         fp.spp = spp;
         sp.rec = s->d_samp;
         sp.rec_jy = s->d_samp_jy;
+        sp.nfeat = nfeat;
+        sp.rec_feat = need_rec;
         if (sp.mode == RT_SPLAT_STREAM) {
             sp.ksmax = ks <= 2 ? 2 : ks <= 4 ? 4 : 12;
             sp.lds = tr_lds_bytes(sp.ksmax);
             const size_t npx = (size_t)w*h;
             const size_t parts = (size_t)std::max(shape.nparts - 1, 0);
-            if (parts && s->partial_cap < parts*npx) {
+            if (parts && s->partial_cap < parts*npx*nfeat) {
                 if (s->d_partials) (void)hipFree(s->d_partials);
                 s->d_partials = nullptr; s->partial_cap = 0;
-                HIP_OK(hipMalloc(&s->d_partials, sizeof(float4)*parts*npx));
-                s->partial_cap = parts*npx;
+                HIP_OK(hipMalloc(&s->d_partials, sizeof(float4)*parts*npx*nfeat));
+                s->partial_cap = parts*npx*nfeat;
             }
             sp.partials = s->d_partials;
             if (L.blocks_ks != ks) {
@@ -5665,7 +5736,7 @@ static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_se
                         for (int x = 0; x < NXCD; ++x)
                             if (start[x] + k < start[x + 1]) blocks.push_back(colmajor[start[x] + k]);
                 }
-                const size_t aux = blocks.size() + 2*MAX_PARTITIONS;       // the pointer table, then the blocks
+                const size_t aux = blocks.size() + AUX_TABLES;             // the pointer tables, then the blocks
                 if (s->aux_cap < aux) {
                     if (s->d_aux) (void)hipFree(s->d_aux);
                     s->d_aux = nullptr; s->aux_cap = 0;
@@ -5673,18 +5744,20 @@ static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_se
                     s->aux_cap = aux;
                     L.aux_parts = -1;
                 }
-                HIP_OK(hipMemcpy(s->d_aux + 2*MAX_PARTITIONS, blocks.data(), sizeof(uint32_t)*blocks.size(), hipMemcpyHostToDevice));
+                HIP_OK(hipMemcpy(s->d_aux + AUX_TABLES, blocks.data(), sizeof(uint32_t)*blocks.size(), hipMemcpyHostToDevice));
                 L.nblocks = (uint32_t)blocks.size();
                 L.blocks_ks = ks;
             }
-            if (L.aux_parts != (int)parts || L.aux_partials != s->d_partials || L.aux_npx != npx) {
-                std::vector<const float4*> part_ptrs;
-                for (size_t k = 0; k < parts; ++k) part_ptrs.push_back(s->d_partials + k*npx);
-                if (parts) HIP_OK(hipMemcpy(s->d_aux, part_ptrs.data(), sizeof(float4*)*parts, hipMemcpyHostToDevice));
-                L.aux_parts = (int)parts; L.aux_partials = s->d_partials; L.aux_npx = npx;
+            if (L.aux_parts != (int)parts || L.aux_partials != s->d_partials || L.aux_npx != npx || L.aux_feat != nfeat) {
+                // feature f's table at MAX_PARTITIONS*f: the addresses of its partitions' buffers
+                std::vector<const float4*> part_ptrs((size_t)MAX_PARTITIONS*nfeat, nullptr);
+                for (int f = 0; f < nfeat; ++f)
+                    for (size_t k = 0; k < parts; ++k) part_ptrs[(size_t)MAX_PARTITIONS*f + k] = s->d_partials + (f*parts + k)*npx;
+                if (parts) HIP_OK(hipMemcpy(s->d_aux, part_ptrs.data(), sizeof(float4*)*part_ptrs.size(), hipMemcpyHostToDevice));
+                L.aux_parts = (int)parts; L.aux_partials = s->d_partials; L.aux_npx = npx; L.aux_feat = nfeat;
             }
             sp.nblocks = L.nblocks;
-            sp.blocks = s->d_aux + 2*MAX_PARTITIONS;
+            sp.blocks = s->d_aux + AUX_TABLES;
             sp.part_ptrs = reinterpret_cast<const float4* const*>(s->d_aux);
             static bool attr_set = false;
             if (!attr_set) {                      // k_resolve_tiles<12> stages up to 72 KB
@@ -5711,8 +5784,12 @@ static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_se
     const bool tall = fp.pixels >= tall_px;
     const int rry = tall ? RES_RY_TALL : RES_RY;
     dim3 rgrid((w + RES_BX - 1) / RES_BX, (h + RES_BY*rry - 1) / (RES_BY*rry));
-    if (tall) k_resolve<RES_RY_TALL><<<rgrid, RES_BX*RES_BY, 0, stream>>>(fp);
-    else k_resolve<RES_RY><<<rgrid, RES_BX*RES_BY, 0, stream>>>(fp);
+    for (int f = 0; f < nfeat; ++f) {                   // a one-pass feature frame: once per record array
+        FrameParams ff = fp;
+        if (f) { ff.samp_rgbx += (size_t)f*need_rec; ff.samp_jy += (size_t)f*need_rec; ff.accum = fp.accum_feat[f - 1]; }
+        if (tall) k_resolve<RES_RY_TALL><<<rgrid, RES_BX*RES_BY, 0, stream>>>(ff);
+        else k_resolve<RES_RY><<<rgrid, RES_BX*RES_BY, 0, stream>>>(ff);
+    }
     HIP_OK(hipGetLastError());
     if (prof_resolve) HIP_OK(hipEventRecord(e1, stream));
     HIP_OK(hipStreamSynchronize(stream));
@@ -5723,7 +5800,7 @@ static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_se
             float ms = 0.0f;
             (void)hipEventElapsedTime(&ms, e0, e1);
             stats->kernel_ms[RT_KERNEL_RESOLVE] += ms;
-            stats->kernel_launches[RT_KERNEL_RESOLVE] += 1;
+            stats->kernel_launches[RT_KERNEL_RESOLVE] += nfeat;
         }
     }
     if (e0) (void)hipEventDestroy(e0);
@@ -5736,7 +5813,7 @@ int rt_render_device(rt_scene* s, const rt_camera* camera, const rt_settings* st
                      uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
                      float* d_pixels, void* hip_stream, rt_stats* stats) {
     return render_frame_device(s, camera, st, filter, tiles, total_frame_index, w, h, frame_count, -1, d_pixels,
-                               hip_stream, stats);
+                               nullptr, hip_stream, stats);
 }
 
 static int check_feature(const char* entry, int feature) {
@@ -5752,7 +5829,7 @@ int rt_render_feature_device(rt_scene* s, const rt_camera* camera, const rt_sett
     int err = check_feature("rt_render_feature_device", feature);
     if (err) return err;
     return render_frame_device(s, camera, st, filter, tiles, total_frame_index, w, h, frame_count, feature, d_pixels,
-                               hip_stream, stats);
+                               nullptr, hip_stream, stats);
 }
 
 int rt_render_feature(rt_scene* s, const rt_camera* camera, const rt_settings* st, const rt_filter_cache* filter,
@@ -5769,6 +5846,80 @@ int rt_render_feature(rt_scene* s, const rt_camera* camera, const rt_settings* s
     if (!err) err = rt_render_feature_device(s, camera, st, filter, tiles, total_frame_index, accum->w, accum->h,
                                              accum->frame_count, feature, d, nullptr, stats);
     if (!err && hipMemcpy(accum->pixels, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) { set_error("copy out"); err = RT_ERROR_DEVICE; }
+    (void)hipFree(d);
+    return err;
+}
+
+// The arguments of the one-pass entries that their own checks name (the rest: render_frame_device's)
+static int features_refuse(const char* entry, const char* what) {
+    set_error(std::string(entry) + ": " + what);
+    return RT_ERROR_INVALID;
+}
+
+int rt_render_features_device(rt_scene* s, const rt_camera* camera, const rt_settings* st,
+                              const rt_filter_cache* filter, const rt_tile_set* tiles,
+                              uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
+                              float* d_normal, float* d_distance, float* d_albedo, void* hip_stream, rt_stats* stats) {
+    const char* const e = "rt_render_features_device";
+    if (!s) return features_refuse(e, "scene is NULL");
+    if (!camera) return features_refuse(e, "camera is NULL");
+    if (!st) return features_refuse(e, "settings is NULL");
+    if (!filter) return features_refuse(e, "filter is NULL");
+    if (!tiles) return features_refuse(e, "tiles is NULL");
+    if (!d_normal) return features_refuse(e, "d_normal is NULL");
+    if (!d_distance) return features_refuse(e, "d_distance is NULL");
+    if (!d_albedo) return features_refuse(e, "d_albedo is NULL");
+    if (d_normal == d_distance) return features_refuse(e, "d_normal and d_distance are the same buffer");
+    if (d_normal == d_albedo) return features_refuse(e, "d_normal and d_albedo are the same buffer");
+    if (d_distance == d_albedo) return features_refuse(e, "d_distance and d_albedo are the same buffer");
+    if (!w) return features_refuse(e, "w is 0");
+    if (!h) return features_refuse(e, "h is 0");
+    float* const more[RT_FEATURE_COUNT - 1] = {d_distance, d_albedo};
+    return render_frame_device(s, camera, st, filter, tiles, total_frame_index, w, h, frame_count, RT_FEATURE_COUNT,
+                               d_normal, more, hip_stream, stats);
+}
+
+int rt_render_features(rt_scene* s, const rt_camera* camera, const rt_settings* st, const rt_filter_cache* filter,
+                       const rt_tile_set* tiles, uint32_t total_frame_index, rt_accumulation_buffer* normal,
+                       rt_accumulation_buffer* distance, rt_accumulation_buffer* albedo, rt_stats* stats) {
+    const char* const e = "rt_render_features";
+    if (!s) return features_refuse(e, "scene is NULL");
+    if (!camera) return features_refuse(e, "camera is NULL");
+    if (!st) return features_refuse(e, "settings is NULL");
+    if (!filter) return features_refuse(e, "filter is NULL");
+    if (!tiles) return features_refuse(e, "tiles is NULL");
+    rt_accumulation_buffer* const buf[RT_FEATURE_COUNT] = {normal, distance, albedo};
+    static const char* const names[RT_FEATURE_COUNT] = {"normal", "distance", "albedo"};
+    for (int f = 0; f < RT_FEATURE_COUNT; ++f)
+        if (!buf[f] || !buf[f]->pixels) return features_refuse(e, (std::string(names[f]) + " is NULL or has no pixels").c_str());
+    for (int f = 1; f < RT_FEATURE_COUNT; ++f) {
+        if (buf[f]->w != normal->w || buf[f]->h != normal->h)
+            return features_refuse(e, (std::string(names[f]) + " differs from normal in w or h").c_str());
+        if (buf[f]->frame_count != normal->frame_count)
+            return features_refuse(e, (std::string(names[f]) + " differs from normal in frame_count").c_str());
+        for (int g = 0; g < f; ++g)
+            if (buf[f]->pixels == buf[g]->pixels)
+                return features_refuse(e, (std::string(names[g]) + " and " + names[f] + " share their pixels").c_str());
+    }
+    if (!normal->w) return features_refuse(e, "w is 0");
+    if (!normal->h) return features_refuse(e, "h is 0");
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
+        set_error("rt_render_features: no HIP device visible");
+        return RT_ERROR_NO_DEVICE;
+    }
+    HIP_OK(hipSetDevice(s->device));
+    const size_t bytes = (size_t)normal->w*normal->h*4*sizeof(float);
+    float* d = nullptr;
+    HIP_OK(hipMalloc(&d, bytes*RT_FEATURE_COUNT));
+    float* const df[RT_FEATURE_COUNT] = {d, d + bytes/sizeof(float), d + 2*(bytes/sizeof(float))};
+    int err = RT_OK;
+    for (int f = 0; f < RT_FEATURE_COUNT && !err; ++f)
+        if (hipMemcpy(df[f], buf[f]->pixels, bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("copy in"); err = RT_ERROR_DEVICE; }
+    if (!err) err = rt_render_features_device(s, camera, st, filter, tiles, total_frame_index, normal->w, normal->h,
+                                              normal->frame_count, df[0], df[1], df[2], nullptr, stats);
+    for (int f = 0; f < RT_FEATURE_COUNT && !err; ++f)
+        if (hipMemcpy(buf[f]->pixels, df[f], bytes, hipMemcpyDeviceToHost) != hipSuccess) { set_error("copy out"); err = RT_ERROR_DEVICE; }
     (void)hipFree(d);
     return err;
 }

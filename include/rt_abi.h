@@ -510,6 +510,25 @@ int rt_render_feature_device(rt_scene* scene, const rt_camera* camera, const rt_
 int rt_render_feature(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
                       const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
                       int feature, rt_accumulation_buffer* accum, rt_stats* stats);
+/* The three feature frames in one walk.  Arguments and accumulation as rt_render_feature_device; samples are
+ * added to each buffer, and after the call buffer f holds what rt_render_feature_device(..., feature = f, ...)
+ * would have added to it: the same records, resolved once per buffer, so in the exact splat mode (and in the
+ * streaming mode under one configuration) the three equal the single-feature frames bit for bit.  The camera
+ * rays, the specular bounces and the frame's ramp-down run once: `stats` describes that one walk (samples and
+ * closest_hit_rays are a single feature frame's, shadow_rays is 0).  A sample leaves three 20-byte records,
+ * so the record budget counts three rings: over it the exact mode streams and the rings shorten, as for any
+ * frame.  All three buffers are required and must be distinct; a NULL scene, camera, settings, filter, tiles or
+ * buffer, two equal buffers and a w or h of 0 are RT_ERROR_INVALID, each named, before the device is touched. */
+int rt_render_features_device(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                              const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                              uint32_t w, uint32_t h, uint32_t frame_count, float* d_normal, float* d_distance,
+                              float* d_albedo, void* hip_stream, rt_stats* stats);
+/* Same, into host memory, as rt_render_feature.  The three buffers must agree in w, h and frame_count
+ * (RT_ERROR_INVALID, named).  RT_ERROR_NO_DEVICE without a GPU (after the argument checks). */
+int rt_render_features(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                       const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                       rt_accumulation_buffer* normal, rt_accumulation_buffer* distance,
+                       rt_accumulation_buffer* albedo, rt_stats* stats);
 
 /* The denoise stage with feature frames: rt_denoise_device's filter (guide 0 = a NORMAL frame, guide 1 = a
  * DISTANCE frame) with an albedo frame, which
@@ -539,7 +558,8 @@ int rt_denoise_features(int device, const rt_accumulation_buffer* beauty, const 
                         const float* albedo, const rt_denoise_features_params* p, float* out_pixels);
 /* rt_render_picture_denoised with feature frames, written on the public entries: the beauty frame; a
  * NORMAL, a DISTANCE and an ALBEDO frame of guide_spp samples per pixel (0: the beauty frame's count) with
- * the same camera, filter, tiles, total_frame_index and max_bounce_count; rt_denoise_features_device;
+ * the same camera, filter, tiles, total_frame_index and max_bounce_count (rendered in one walk by
+ * rt_render_features_device: the three rt_render_feature_device frames, bit for bit); rt_denoise_features_device;
  * rt_postprocess_device with the dither texture of total_frame_index + 1.  `stats` is the beauty frame's. */
 int rt_render_picture_features_denoised(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
                                         const rt_filter_cache* filter, const rt_tile_set* tiles,
