@@ -22,7 +22,8 @@ import numpy as np
 
 from . import abi
 from .abi import (V3, v3, M4x4Inv, Material, Camera, Settings, FilterCache, PostSettings, TileSet, Stats,
-                  AccumulationBuffer, RayQuery, HitRecord, BvhInfo, DenoiseParams, DenoiseFeaturesParams)
+                  AccumulationBuffer, RayQuery, HitRecord, BvhInfo, DenoiseParams, DenoiseFeaturesParams,
+                  TileErrorParams, AdaptiveParams)
 
 __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settings", "load_reconstruction_kernel",
            "translate", "scale", "rotate_x", "rotate_y", "rotate_z", "identity", "aim_camera", "aim_camera_at",
@@ -30,7 +31,8 @@ __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settin
            "set_splat_mode", "splat_mode", "take_picture", "read_bitmap", "integrator_name", "find_integrator",
            "integrator_supported", "scene_integrator_supported", "DenoiseParams", "default_denoise_params", "denoise",
            "denoise_workspace_bytes", "DenoiseFeaturesParams", "default_denoise_features_params", "denoise_features",
-           "denoise_features_workspace_bytes"]
+           "denoise_features_workspace_bytes", "TileErrorParams", "AdaptiveParams", "default_tile_error_params",
+           "default_adaptive_params", "adaptive_workspace_bytes", "tile_error"]
 
 PI_32 = 3.14159265359
 DEG_TO_RAD = 6.28318530717 / 360.0
@@ -439,6 +441,63 @@ class DeviceScene:
                                                 out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(stats)))
         return out, stats
 
+    def render_tiles(self, camera, settings, filter_cache, w, h, tile_ids, accum=None, frame_count=0,
+                     total_frame_index=0, tile=64):
+        """rt_render_tiles: adds the frame of the listed tiles (strictly ascending indices into the tile grid)
+        into `accum` (float32 [h,w,4], host) -> (accum, stats)."""
+        if accum is None:
+            accum = np.zeros((h, w, 4), np.float32)
+        assert accum.dtype == np.float32 and accum.flags.c_contiguous and accum.shape == (h, w, 4)
+        ids = np.ascontiguousarray(tile_ids, np.uint32).reshape(-1)
+        buf = AccumulationBuffer(w, h, frame_count, accum.ctypes.data_as(C.POINTER(C.c_float)))
+        stats = Stats()
+        _check(lib().rt_render_tiles(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache), tile, tile,
+                                     ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.size, total_frame_index,
+                                     C.byref(buf), C.byref(stats)))
+        return accum, stats
+
+    def render_tiles_device(self, camera, settings, filter_cache, w, h, tile_ids, d_pixels, stream=None, frame_count=0,
+                            total_frame_index=0, tile=64):
+        """rt_render_tiles_device into a device pointer (e.g. torch tensor .data_ptr()); tile_ids is a host list."""
+        ids = np.ascontiguousarray(tile_ids, np.uint32).reshape(-1)
+        stats = Stats()
+        _check(lib().rt_render_tiles_device(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache), tile, tile,
+                                            ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.size, total_frame_index, w, h,
+                                            frame_count, C.c_void_p(d_pixels), C.c_void_p(stream) if stream else None,
+                                            C.byref(stats)))
+        return stats
+
+    def render_adaptive(self, camera, settings, filter_cache, w, h, params=None, accum=None, frame_count=0,
+                        total_frame_index=0, tile=64):
+        """rt_render_adaptive: adaptive sampling by tiles (settings.samples_per_pixel is ignored, params.max_spp
+        rules) added into `accum` (float32 [h,w,4], host) -> (accum, tile_spp, stats), tile_spp the samples each
+        tile of the grid took (uint32 [tcy, tcx])."""
+        if params is None:
+            params = default_adaptive_params()
+        if accum is None:
+            accum = np.zeros((h, w, 4), np.float32)
+        assert accum.dtype == np.float32 and accum.flags.c_contiguous and accum.shape == (h, w, 4)
+        tile_spp = np.zeros(((h + tile - 1) // tile, (w + tile - 1) // tile), np.uint32)
+        buf = AccumulationBuffer(w, h, frame_count, accum.ctypes.data_as(C.POINTER(C.c_float)))
+        stats = Stats()
+        _check(lib().rt_render_adaptive(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache), tile, tile,
+                                        total_frame_index, C.byref(params), C.byref(buf),
+                                        tile_spp.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(stats)))
+        return accum, tile_spp, stats
+
+    def render_adaptive_device(self, camera, settings, filter_cache, w, h, params, d_pixels, d_workspace=None,
+                               stream=None, frame_count=0, total_frame_index=0, tile=64):
+        """rt_render_adaptive_device into a device pointer; d_workspace: adaptive_workspace_bytes(w, h, tile) bytes
+        on the device, or None -> (tile_spp, stats)."""
+        tile_spp = np.zeros(((h + tile - 1) // tile, (w + tile - 1) // tile), np.uint32)
+        stats = Stats()
+        _check(lib().rt_render_adaptive_device(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache), tile,
+                                               tile, total_frame_index, w, h, frame_count, C.byref(params),
+                                               C.c_void_p(d_workspace) if d_workspace else None, C.c_void_p(d_pixels),
+                                               tile_spp.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                               C.c_void_p(stream) if stream else None, C.byref(stats)))
+        return tile_spp, stats
+
     def configure(self, **fields):
         """rt_scene_set_config with the named fields changed, e.g. configure(partitions=1,
         splat_mode=abi.RT_SPLAT_EXACT).  Returns the previous configuration (pass it to
@@ -567,6 +626,45 @@ def denoise_features(accum, normal=None, distance=None, albedo=None, params=None
                                      *[g.ctypes.data_as(fp) if g is not None else None for g in frames],
                                      C.byref(params), out.ctypes.data_as(fp)))
     return out
+
+
+def default_tile_error_params():
+    """rt_tile_error_default_params (no device needed) -> TileErrorParams."""
+    p = TileErrorParams()
+    _check(lib().rt_tile_error_default_params(C.byref(p)))
+    return p
+
+
+def default_adaptive_params():
+    """rt_adaptive_default_params (no device needed) -> AdaptiveParams."""
+    p = AdaptiveParams()
+    _check(lib().rt_adaptive_default_params(C.byref(p)))
+    return p
+
+
+def adaptive_workspace_bytes(w, h, tile=64):
+    """rt_adaptive_workspace_bytes (no device needed): the two half buffers and the per-tile lists."""
+    return int(lib().rt_adaptive_workspace_bytes(w, h, tile, tile))
+
+
+def tile_error(half_a, half_b, tile=64, tile_ids=None, params=None, device=0):
+    """The tile error estimate on the GPU (rt_tile_error): two host float4 accumulation buffers (h, w, 4) holding
+    disjoint halves of the samples -> (error float32, valid uint32), per listed tile (None: every tile)."""
+    a = np.ascontiguousarray(half_a, np.float32)
+    b = np.ascontiguousarray(half_b, np.float32)
+    assert a.shape == b.shape
+    h, w, _ = a.shape
+    if params is None:
+        params = default_tile_error_params()
+    ids = None if tile_ids is None else np.ascontiguousarray(tile_ids, np.uint32).reshape(-1)
+    count = ((w + tile - 1) // tile)*((h + tile - 1) // tile) if ids is None else ids.size
+    err = np.zeros(count, np.float32)
+    valid = np.zeros(count, np.uint32)
+    fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    _check(lib().rt_tile_error(device, a.ctypes.data_as(fp), b.ctypes.data_as(fp), w, h, tile, tile,
+                               None if ids is None else ids.ctypes.data_as(up), count, C.byref(params),
+                               err.ctypes.data_as(fp), valid.ctypes.data_as(up)))
+    return err, valid
 
 
 def write_bitmap(path, bgra):

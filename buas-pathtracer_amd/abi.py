@@ -201,6 +201,15 @@ class DenoiseFeaturesParams(C.Structure):     # rt_denoise_features_params (the 
                 ("albedo_floor", C.c_float), ("reserved", C.c_int32 * 5)]
 
 
+class TileErrorParams(C.Structure):    # rt_tile_error_params (adaptive sampling: the tile error estimate)
+    _fields_ = [("floor", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class AdaptiveParams(C.Structure):     # rt_adaptive_params (adaptive sampling: the driver)
+    _fields_ = [("min_spp", C.c_uint32), ("max_spp", C.c_uint32), ("step_spp", C.c_uint32), ("threshold", C.c_float),
+                ("error", TileErrorParams), ("reserved", C.c_int32 * 4)]
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("node_count", C.c_uint32), ("leaf_count", C.c_uint32), ("max_depth", C.c_uint32),
                 ("max_leaf_size", C.c_uint32)]
@@ -283,6 +292,23 @@ ABI_FUNCTIONS = {
     "rt_render_picture_features_denoised": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet),
                                                       C.c_uint32, C.c_uint32, C.c_uint32, P(PostSettings),
                                                       P(DenoiseFeaturesParams), C.c_uint32, P(C.c_uint32), P(Stats)]),
+    "rt_render_tiles_device": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), C.c_uint32, C.c_uint32,
+                                         P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.c_void_p, C.c_void_p, P(Stats)]),
+    "rt_render_tiles": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), C.c_uint32, C.c_uint32,
+                                  P(C.c_uint32), C.c_uint32, C.c_uint32, P(AccumulationBuffer), P(Stats)]),
+    "rt_tile_error_default_params": (C.c_int, [P(TileErrorParams)]),
+    "rt_tile_error_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       C.c_void_p, C.c_uint32, P(TileErrorParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_tile_error": (C.c_int, [C.c_int, P(C.c_float), P(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                P(C.c_uint32), C.c_uint32, P(TileErrorParams), P(C.c_float), P(C.c_uint32)]),
+    "rt_adaptive_default_params": (C.c_int, [P(AdaptiveParams)]),
+    "rt_adaptive_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rt_render_adaptive_device": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), C.c_uint32, C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(AdaptiveParams),
+                                            C.c_void_p, C.c_void_p, P(C.c_uint32), C.c_void_p, P(Stats)]),
+    "rt_render_adaptive": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), C.c_uint32, C.c_uint32,
+                                     C.c_uint32, P(AdaptiveParams), P(AccumulationBuffer), P(C.c_uint32), P(Stats)]),
 }
 
 HOST_FUNCTIONS = {

@@ -8,5 +8,6 @@
 void rt_internal_set_error(const char* message);        // the thread's rt_last_error() message
 int  rt_internal_bind_device(int device);               // hipSetDevice with the ABI's checks: an rt_status
 int  rt_internal_scene_device(const rt_scene* scene);   // the device rt_scene_upload put the scene on
+int  rt_internal_scene_cancelled(const rt_scene* scene); // rt_cancel's flag: set until the next frame's loop starts
 
 #endif

@@ -3920,6 +3920,7 @@ struct rt_scene {
     struct Layout {
         bool valid = false;
         uint32_t w = 0, h = 0, tw = 0, th = 0, si = 0, sc = 0;
+        bool listed = false;                // ids is a caller's list (rt_render_tiles_device), not a shard's tiles
         std::vector<uint32_t> ids, prefix;
         uint64_t owned_px = 0;
         std::vector<int32_t> base;
@@ -5490,10 +5491,13 @@ int rt_postprocess(int device, const rt_accumulation_buffer* accum, const rt_pos
 // rt_render_features_device (feature == RT_FEATURE_COUNT): the three feature frames in one walk, NORMAL into
 // d_pixels and DISTANCE and ALBEDO into d_more[0..1]; a sample leaves three records, so the splat is planned
 // for three rings (or three whole-frame arrays) and resolved once per ring.
+// rt_render_tiles_device (`list` set): the frame of the caller's tiles, `list` holding their ids in descending
+// order (checked by the entry) and `tiles` the tile size with one shard.
 static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_settings* st,
                                const rt_filter_cache* filter, const rt_tile_set* tiles,
                                uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
-                               int feature, float* d_pixels, float* const* d_more, void* hip_stream, rt_stats* stats) {
+                               int feature, float* d_pixels, float* const* d_more, void* hip_stream, rt_stats* stats,
+                               const std::vector<uint32_t>* list = nullptr) {
     if (!s || !camera || !tiles || !d_pixels || !w || !h) { set_error("null argument"); return RT_ERROR_INVALID; }
     const int nfeat = feature == RT_FEATURE_COUNT ? RT_FEATURE_COUNT : 1;
     rt_settings feat_st;
@@ -5527,14 +5531,18 @@ static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_se
     const bool by_pass = shard_mode == RT_SHARD_PASSES && tiles->shard_count > 1;
     const uint32_t tsi = by_pass ? 0u : tiles->shard_index, tsc = by_pass ? 1u : tiles->shard_count;
     auto& L = s->layout;
+    // a caller's list is compared itself (L.ids is the stored copy): another list of the same frame is another layout
     const bool same = L.valid && L.w == w && L.h == h && L.tw == tiles->tile_w && L.th == tiles->tile_h &&
-                      L.si == tsi && L.sc == tsc;
+                      L.si == tsi && L.sc == tsc && L.listed == (list != nullptr) && (!list || L.ids == *list);
     if (!same) {
-        // owned tiles: t % shard_count == shard_index, descending like the reference's queue (:555)
+        // owned tiles: t % shard_count == shard_index (or the caller's list), descending like the reference's
+        // queue (:555)
         L.valid = false;
         L.ids.clear(); L.prefix.assign(1, 0); L.owned_px = 0;
-        for (uint32_t t = fp.tcx*tcy; t-- > 0;) {
-            if (t % tsc != tsi) continue;
+        const size_t nlist = list ? list->size() : (size_t)fp.tcx*tcy;
+        for (size_t i = 0; i < nlist; ++i) {
+            const uint32_t t = list ? (*list)[i] : (uint32_t)(nlist - 1 - i);
+            if (!list && t % tsc != tsi) continue;
             uint32_t min_x = tiles->tile_w*(t % fp.tcx), min_y = tiles->tile_h*(t / fp.tcx);
             uint32_t tw = std::min(w, min_x + tiles->tile_w) - min_x, th = std::min(h, min_y + tiles->tile_h) - min_y;
             L.ids.push_back(t);
@@ -5585,6 +5593,7 @@ static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_se
         k_pixel_map<<<fp.ntiles, 256, 0, stream>>>(fp, s->d_pixmap);
         HIP_OK(hipGetLastError());
         L.w = w; L.h = h; L.tw = tiles->tile_w; L.th = tiles->tile_h; L.si = tsi; L.sc = tsc;
+        L.listed = list != nullptr;
         L.blocks_ks = -1;
         L.valid = true;
     }
@@ -5769,7 +5778,8 @@ static int render_frame_device(rt_scene* s, const rt_camera* camera, const rt_se
         }
     }
     if (debug_timing()) fprintf(stderr, "[rt timing] rt_render_device: layout + splat plan %.3f ms\n", host_ms() - t_entry);
-    err = run_frame(s, st, fp, total, stream, sp, stats, tiles->shard_count > 1);
+    // a list that leaves tiles out is scheduled like a rank's share of a frame
+    err = run_frame(s, st, fp, total, stream, sp, stats, tiles->shard_count > 1 || (list && list->size() < ntile_all));
     if (debug_timing()) fprintf(stderr, "[rt timing] rt_render_device: frame done %.3f ms after entry\n", host_ms() - t_entry);
     if (err || sp.mode != RT_SPLAT_EXACT) {
         if (!err) HIP_OK(hipStreamSynchronize(stream));      // the frame (and its last resolve, combine) is done
@@ -5935,6 +5945,76 @@ int rt_render(rt_scene* s, const rt_camera* camera, const rt_settings* st, const
     if (hipMemcpy(d, accum->pixels, bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("copy in"); err = RT_ERROR_DEVICE; }
     if (!err) err = rt_render_device(s, camera, st, filter, tiles, total_frame_index, accum->w, accum->h,
                                      accum->frame_count, d, nullptr, stats);
+    if (!err && hipMemcpy(accum->pixels, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) { set_error("copy out"); err = RT_ERROR_DEVICE; }
+    (void)hipFree(d);
+    return err;
+}
+
+// The checks of rt_render_tiles_device / rt_render_tiles, all before the device is touched: the frame and
+// tile sizes and the list first (they need no scene), then the pointers.  `desc`: the list, descending.
+static int check_tile_list(const char* e, uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h,
+                           const uint32_t* tile_ids, uint32_t tile_count, std::vector<uint32_t>& desc) {
+    auto refuse = [&](const std::string& what) { set_error(std::string(e) + ": " + what); return RT_ERROR_INVALID; };
+    if (!w) return refuse("w is 0");
+    if (!h) return refuse("h is 0");
+    if (!tile_w) return refuse("tile_w is 0");
+    if (!tile_h) return refuse("tile_h is 0");
+    if (w > 65535 || h > 65535) return refuse("w or h larger than 65535 pixels");
+    if (tile_count && !tile_ids) return refuse("null tile_ids with tile_count > 0");
+    const uint64_t ntiles = (uint64_t)((w + tile_w - 1) / tile_w)*((h + tile_h - 1) / tile_h);
+    for (uint32_t i = 0; i < tile_count; ++i) {
+        if (tile_ids[i] >= ntiles)
+            return refuse("tile_ids[" + std::to_string(i) + "] = " + std::to_string(tile_ids[i]) + " is out of range: the frame has " +
+                          std::to_string(ntiles) + " tiles");
+        if (i && tile_ids[i] <= tile_ids[i - 1])
+            return refuse("tile_ids is not strictly ascending at [" + std::to_string(i) + "]");
+    }
+    desc.clear();
+    for (uint32_t i = tile_count; i-- > 0;) desc.push_back(tile_ids[i]);
+    return RT_OK;
+}
+
+int rt_render_tiles_device(rt_scene* s, const rt_camera* camera, const rt_settings* st, const rt_filter_cache* filter,
+                           uint32_t tile_w, uint32_t tile_h, const uint32_t* tile_ids, uint32_t tile_count,
+                           uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
+                           float* d_pixels, void* hip_stream, rt_stats* stats) {
+    const char* e = "rt_render_tiles_device";
+    std::vector<uint32_t> desc;
+    int err = check_tile_list(e, w, h, tile_w, tile_h, tile_ids, tile_count, desc);
+    if (err) return err;
+    auto null_arg = [&](const char* what) { set_error(std::string(e) + ": null " + what); return RT_ERROR_INVALID; };
+    if (!s) return null_arg("scene");
+    if (!camera) return null_arg("camera");
+    if (!st) return null_arg("settings");
+    if (!filter) return null_arg("filter");
+    if (!d_pixels) return null_arg("d_pixels");
+    if (!tile_count) { if (stats) memset(stats, 0, sizeof(*stats)); return RT_OK; }
+    const rt_tile_set tiles = {tile_w, tile_h, 0u, 1u};
+    return render_frame_device(s, camera, st, filter, &tiles, total_frame_index, w, h, frame_count, -1, d_pixels,
+                               nullptr, hip_stream, stats, &desc);
+}
+
+int rt_render_tiles(rt_scene* s, const rt_camera* camera, const rt_settings* st, const rt_filter_cache* filter,
+                    uint32_t tile_w, uint32_t tile_h, const uint32_t* tile_ids, uint32_t tile_count,
+                    uint32_t total_frame_index, rt_accumulation_buffer* accum, rt_stats* stats) {
+    const char* e = "rt_render_tiles";
+    if (!accum || !accum->pixels) { set_error(std::string(e) + ": null accum"); return RT_ERROR_INVALID; }
+    std::vector<uint32_t> desc;
+    int err = check_tile_list(e, accum->w, accum->h, tile_w, tile_h, tile_ids, tile_count, desc);
+    if (err) return err;
+    auto null_arg = [&](const char* what) { set_error(std::string(e) + ": null " + what); return RT_ERROR_INVALID; };
+    if (!s) return null_arg("scene");
+    if (!camera) return null_arg("camera");
+    if (!st) return null_arg("settings");
+    if (!filter) return null_arg("filter");
+    if (!tile_count) { if (stats) memset(stats, 0, sizeof(*stats)); return RT_OK; }
+    HIP_OK(hipSetDevice(s->device));
+    size_t bytes = (size_t)accum->w*accum->h*4*sizeof(float);
+    float* d = nullptr;
+    HIP_OK(hipMalloc(&d, bytes));
+    if (hipMemcpy(d, accum->pixels, bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("copy in"); err = RT_ERROR_DEVICE; }
+    if (!err) err = rt_render_tiles_device(s, camera, st, filter, tile_w, tile_h, tile_ids, tile_count, total_frame_index,
+                                           accum->w, accum->h, accum->frame_count, d, nullptr, stats);
     if (!err && hipMemcpy(accum->pixels, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) { set_error("copy out"); err = RT_ERROR_DEVICE; }
     (void)hipFree(d);
     return err;
@@ -6133,3 +6213,4 @@ int rt_debug_intersect(rt_scene* s, uint32_t count, const rt_ray_query* rays, in
 void rt_internal_set_error(const char* message) { set_error(message); }
 int rt_internal_bind_device(int device) { return bind_device(device); }
 int rt_internal_scene_device(const rt_scene* scene) { return scene->device; }
+int rt_internal_scene_cancelled(const rt_scene* scene) { return scene->cancel; }

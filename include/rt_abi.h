@@ -567,6 +567,99 @@ int rt_render_picture_features_denoised(rt_scene* scene, const rt_camera* camera
                                         const rt_post_settings* post, const rt_denoise_features_params* p,
                                         uint32_t guide_spp, uint32_t* out_bgra, rt_stats* stats);
 
+/* Adaptive sampling by tiles: frames over an explicit tile list, a per-tile error estimate, and a driver that
+ * loops the two until every tile is under a threshold or has taken max_spp samples.  Beyond the reference,
+ * which gives every pixel samples_per_pixel samples: an opt-in of new entries only (no existing struct or
+ * entry changes; RT_ABI_VERSION stays).  DESIGN.md ("Adaptive sampling by tiles") defines all three; the
+ * error estimate matches the plain-C restatement tests/ref_adaptive/ref_adaptive.c bit for bit.
+ *
+ * 1. rt_render_tiles_device: rt_render_device for the tiles of `tile_ids` (tile_count indices into the
+ * reference's tile grid: tile t is column t % tcx, row t / tcx, tcx = ceil(w / tile_w)) instead of a shard's.
+ * The listed tiles are rendered in descending order, the reference's queue order, and their samples splat into
+ * every pixel the filter reaches, halos into unlisted tiles included.  A sample's key is (total_frame_index,
+ * frame_count, tile, pixel, sample) as ever, so a tile rendered alone draws the samples the whole frame draws
+ * there.  Any integrator the scene supports; sharding does not apply (no rt_tile_set; rt_set_shard_mode has no
+ * meaning here).  tile_count == 0 is RT_OK with zeroed stats.  RT_ERROR_INVALID, naming the field, before the
+ * device is touched: w, h, tile_w or tile_h of 0, a NULL list with tile_count > 0, an id >= tcx*tcy, a list
+ * that is not strictly ascending (a duplicate included), and a NULL scene, camera, settings, filter or buffer
+ * (checked in this order: the list's checks need no scene). */
+int rt_render_tiles_device(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                           const rt_filter_cache* filter, uint32_t tile_w, uint32_t tile_h,
+                           const uint32_t* tile_ids, uint32_t tile_count, uint32_t total_frame_index,
+                           uint32_t w, uint32_t h, uint32_t frame_count, float* d_pixels, void* hip_stream,
+                           rt_stats* stats);
+/* Same, into host memory, as rt_render (w, h and frame_count are accum's). */
+int rt_render_tiles(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                    const rt_filter_cache* filter, uint32_t tile_w, uint32_t tile_h,
+                    const uint32_t* tile_ids, uint32_t tile_count, uint32_t total_frame_index,
+                    rt_accumulation_buffer* accum, rt_stats* stats);
+
+/* 2. rt_tile_error_device: the half-buffer error of Dammertz et al. (HPG 2010; Cycles' criterion too) per
+ * tile.  A and B are two w*h float4 accumulation buffers (sum w*rgb, sum w) holding disjoint halves of the
+ * samples.  Per pixel of a tile: valid when both weights are > 0.001f and all eight floats are finite;
+ *   a = A.xyz / A.w,  b = B.xyz / B.w,  m = (A.xyz + B.xyz) / (A.w + B.w),
+ *   e = (|a.r - b.r| + |a.g - b.g| + |a.b - b.b|) / sqrtf(max(m.r + m.g + m.b, floor)).
+ * Per tile: tile_error = sum e / n_valid (+INFINITY when no pixel is valid, so a threshold never retires the
+ * tile) and tile_valid = n_valid.  d_tile_ids (device, tile_count ids < tcx*tcy in any order) or NULL for
+ * every tile (tile_count must then be tcx*tcy); the outputs (device) are indexed by position in the list.
+ * One workgroup per tile and one fixed summation order: a pure function of the two buffers.
+ * RT_ERROR_INVALID by name for a NULL buffer, parameter or output pointer, w, h, tile_w or tile_h of 0, a
+ * tile_count of 0 or above tcx*tcy (or other than tcx*tcy with a NULL list), and a floor that is not finite
+ * and > 0: all before the device is touched.  An id out of range on the device gives +INFINITY and 0. */
+typedef struct rt_tile_error_params {
+    float   floor;             /* lower bound of m.r + m.g + m.b under the root; default 1e-4f */
+    int32_t reserved[3];
+} rt_tile_error_params;
+int rt_tile_error_default_params(rt_tile_error_params* out);               /* no device needed */
+int rt_tile_error_device(int device, const float* d_half_a, const float* d_half_b, uint32_t w, uint32_t h,
+                         uint32_t tile_w, uint32_t tile_h, const uint32_t* d_tile_ids, uint32_t tile_count,
+                         const rt_tile_error_params* p, float* d_tile_error, uint32_t* d_tile_valid,
+                         void* hip_stream);
+/* Same, from and to host memory (tile_ids host or NULL; the list's ids are checked on the host).
+ * RT_ERROR_NO_DEVICE without a GPU (after the argument checks). */
+int rt_tile_error(int device, const float* half_a, const float* half_b, uint32_t w, uint32_t h,
+                  uint32_t tile_w, uint32_t tile_h, const uint32_t* tile_ids, uint32_t tile_count,
+                  const rt_tile_error_params* p, float* tile_error, uint32_t* tile_valid);
+
+/* 3. rt_render_adaptive_device: written on the two above.  settings->samples_per_pixel is ignored; max_spp
+ * rules.  The active list starts as every tile.  Round r = 0, 1, ... while tiles are active and
+ * r*step_spp < max_spp: the active list is rendered into half buffer A with frame_count + r*step_spp and
+ * step_spp/2 samples, and into half buffer B with frame_count + r*step_spp + step_spp/2 and step_spp/2
+ * samples (rt_render_tiles_device both: together the samples a uniform frame of step_spp samples at
+ * frame_count + r*step_spp draws in those tiles); once (r+1)*step_spp >= min_spp, rt_tile_error_device runs
+ * over the active list, the errors are read back, and tiles with error <= threshold leave the list.  At the
+ * end one kernel adds A + B into d_pixels (samples are added, as in every render entry).  out_tile_spp[t]
+ * (host, tcx*tcy, may be NULL) is the samples tile t took.  The counters of `stats` are sums over the calls,
+ * `seconds` the wall time of the whole call, splat_mode and shadow_launch the last frame's.  rt_cancel ends
+ * the loop with RT_ERROR_CANCELLED (d_pixels is then untouched).  The workspace is two w*h float4 buffers and
+ * the per-tile lists (rt_adaptive_workspace_bytes); with NULL the call allocates and frees its own.
+ * RT_ERROR_INVALID by name before the device is touched: a NULL parameter, scene, camera, settings, filter or
+ * buffer; step_spp 0 or odd; min_spp or max_spp of 0 or no multiple of step_spp; min_spp > max_spp; a
+ * threshold that is negative or not finite; a bad error floor; w, h, tile_w or tile_h of 0.
+ * rt_adaptive_default_params: min_spp 16, max_spp 256, step_spp 16, floor 1e-4f, and threshold 0.5f: the value
+ * at which C3 at 480x270 takes the samples of a 64 to 128 spp uniform frame (DESIGN.md section 6 has the table).
+ * It is a budget, not a quality claim: at equal samples the uniform frame measured as good or better on C3 and
+ * C4, so choose the threshold per scene.  A frame costs about 2.4 ms whatever it renders, so a round (two
+ * frames and an estimate) should carry some millions of samples: raise step_spp for frames under 1080p. */
+typedef struct rt_adaptive_params {
+    uint32_t min_spp, max_spp, step_spp;   /* step_spp even and > 0; min_spp <= max_spp; both multiples of step_spp */
+    float    threshold;                    /* a tile retires when its error <= threshold; >= 0, finite */
+    rt_tile_error_params error;
+    int32_t  reserved[4];
+} rt_adaptive_params;
+int    rt_adaptive_default_params(rt_adaptive_params* out);                                     /* no device needed */
+size_t rt_adaptive_workspace_bytes(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h);   /* no device needed */
+int rt_render_adaptive_device(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                              const rt_filter_cache* filter, uint32_t tile_w, uint32_t tile_h,
+                              uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
+                              const rt_adaptive_params* p, void* d_workspace, float* d_pixels,
+                              uint32_t* out_tile_spp, void* hip_stream, rt_stats* stats);
+/* Same, into host memory, as rt_render (w, h and frame_count are accum's). */
+int rt_render_adaptive(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                       const rt_filter_cache* filter, uint32_t tile_w, uint32_t tile_h, uint32_t total_frame_index,
+                       const rt_adaptive_params* p, rt_accumulation_buffer* accum, uint32_t* out_tile_spp,
+                       rt_stats* stats);
+
 /* The reference's top-down BVH builders on the device (RT/bvh.cpp:222-326 with
  * partition_midpoint :53-61, partition_sah_binned :138-213 or the full SAH sweep
  * partition_objects_sah / evaluate_sah :63-131, the partition of :26-51): one launch per
