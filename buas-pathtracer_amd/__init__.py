@@ -23,7 +23,7 @@ import numpy as np
 from . import abi
 from .abi import (V3, v3, M4x4Inv, Material, Camera, Settings, FilterCache, PostSettings, TileSet, Stats,
                   AccumulationBuffer, RayQuery, HitRecord, BvhInfo, DenoiseParams, DenoiseFeaturesParams,
-                  TileErrorParams, AdaptiveParams)
+                  TileErrorParams, AdaptiveParams, RobustParams)
 
 __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settings", "load_reconstruction_kernel",
            "translate", "scale", "rotate_x", "rotate_y", "rotate_z", "identity", "aim_camera", "aim_camera_at",
@@ -32,7 +32,8 @@ __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settin
            "integrator_supported", "scene_integrator_supported", "DenoiseParams", "default_denoise_params", "denoise",
            "denoise_workspace_bytes", "DenoiseFeaturesParams", "default_denoise_features_params", "denoise_features",
            "denoise_features_workspace_bytes", "TileErrorParams", "AdaptiveParams", "default_tile_error_params",
-           "default_adaptive_params", "adaptive_workspace_bytes", "tile_error"]
+           "default_adaptive_params", "adaptive_workspace_bytes", "tile_error", "RobustParams", "default_robust_params",
+           "robust_workspace_bytes", "robust_combine"]
 
 PI_32 = 3.14159265359
 DEG_TO_RAD = 6.28318530717 / 360.0
@@ -498,6 +499,51 @@ class DeviceScene:
                                                C.c_void_p(stream) if stream else None, C.byref(stats)))
         return tile_spp, stats
 
+    def render_robust(self, camera, settings, filter_cache, w, h, params=None, frame_count=0, total_frame_index=0,
+                      tile=64, shard_index=0, shard_count=1, want_info=True):
+        """rt_render_robust: the frame of settings.samples_per_pixel samples rendered as its params.buffers shards by
+        sample passes, combined by the robust estimator -> (out float32 [h,w,4] = {r, g, b, 1}, info float32 [h,w,4] = {G, c, n, weight} or None, stats)."""
+        if params is None:
+            params = default_robust_params()
+        out = np.zeros((h, w, 4), np.float32)
+        info = np.zeros((h, w, 4), np.float32) if want_info else None
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        fp = C.POINTER(C.c_float)
+        _check(lib().rt_render_robust(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache), C.byref(tiles),
+                                      total_frame_index, w, h, frame_count, C.byref(params), out.ctypes.data_as(fp),
+                                      info.ctypes.data_as(fp) if want_info else None, C.byref(stats)))
+        return out, info, stats
+
+    def render_robust_device(self, camera, settings, filter_cache, w, h, params, d_out, d_info=None, d_workspace=None,
+                             stream=None, frame_count=0, total_frame_index=0, tile=64, shard_index=0, shard_count=1):
+        """rt_render_robust_device into device pointers (d_out is overwritten); d_workspace:
+        robust_workspace_bytes(w, h, params.buffers) bytes on the device, or None -> stats."""
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        _check(lib().rt_render_robust_device(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                             C.byref(tiles), total_frame_index, w, h, frame_count, C.byref(params),
+                                             C.c_void_p(d_workspace) if d_workspace else None, C.c_void_p(d_out),
+                                             C.c_void_p(d_info) if d_info else None,
+                                             C.c_void_p(stream) if stream else None, C.byref(stats)))
+        return stats
+
+    def render_picture_robust(self, camera, settings, filter_cache, w, h, post, params=None, denoise_params=None,
+                              guide_spp=0, total_frame_index=0, tile=64, shard_index=0, shard_count=1):
+        """rt_render_picture_robust: rt_render_picture with the robust estimator in place of the mean and, with
+        `denoise_params` (DenoiseFeaturesParams), the denoise stage with feature frames on its output
+        -> (BGRA8 (h, w) u32, the driver's stats)."""
+        if params is None:
+            params = default_robust_params()
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        out = np.zeros((h, w), np.uint32)
+        stats = Stats()
+        _check(lib().rt_render_picture_robust(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                              C.byref(tiles), total_frame_index, w, h, C.byref(post), C.byref(params),
+                                              C.byref(denoise_params) if denoise_params is not None else None, guide_spp,
+                                              out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(stats)))
+        return out, stats
+
     def configure(self, **fields):
         """rt_scene_set_config with the named fields changed, e.g. configure(partitions=1,
         splat_mode=abi.RT_SPLAT_EXACT).  Returns the previous configuration (pass it to
@@ -665,6 +711,33 @@ def tile_error(half_a, half_b, tile=64, tile_ids=None, params=None, device=0):
                                None if ids is None else ids.ctypes.data_as(up), count, C.byref(params),
                                err.ctypes.data_as(fp), valid.ctypes.data_as(up)))
     return err, valid
+
+
+def default_robust_params():
+    """rt_robust_default_params (no device needed) -> RobustParams."""
+    p = RobustParams()
+    _check(lib().rt_robust_default_params(C.byref(p)))
+    return p
+
+
+def robust_workspace_bytes(w, h, buffers=8):
+    """rt_robust_workspace_bytes (no device needed): the stack, buffers*w*h*16 bytes."""
+    return int(lib().rt_robust_workspace_bytes(w, h, buffers))
+
+
+def robust_combine(stack, params=None, device=0, want_info=True):
+    """The robust estimator on the GPU (rt_robust_combine): a host stack of K float4 accumulation buffers
+    (K, h, w, 4) holding disjoint sample sets of one frame -> (out (h, w, 4), info (h, w, 4) or None)."""
+    stack = np.ascontiguousarray(stack, np.float32)
+    k, h, w, _ = stack.shape
+    if params is None:
+        params = default_robust_params()
+    out = np.zeros((h, w, 4), np.float32)
+    info = np.zeros((h, w, 4), np.float32) if want_info else None
+    fp = C.POINTER(C.c_float)
+    _check(lib().rt_robust_combine(device, stack.ctypes.data_as(fp), k, w, h, C.byref(params), out.ctypes.data_as(fp),
+                                   info.ctypes.data_as(fp) if want_info else None))
+    return out, info
 
 
 def write_bitmap(path, bgra):

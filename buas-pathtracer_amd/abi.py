@@ -210,6 +210,10 @@ class AdaptiveParams(C.Structure):     # rt_adaptive_params (adaptive sampling: 
                 ("error", TileErrorParams), ("reserved", C.c_int32 * 4)]
 
 
+class RobustParams(C.Structure):       # rt_robust_params (the robust estimator: a Gini-adaptive median of means)
+    _fields_ = [("buffers", C.c_uint32), ("gini_scale", C.c_float), ("max_trim", C.c_uint32), ("reserved", C.c_int32 * 5)]
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("node_count", C.c_uint32), ("leaf_count", C.c_uint32), ("max_depth", C.c_uint32),
                 ("max_leaf_size", C.c_uint32)]
@@ -309,6 +313,21 @@ ABI_FUNCTIONS = {
                                             C.c_void_p, C.c_void_p, P(C.c_uint32), C.c_void_p, P(Stats)]),
     "rt_render_adaptive": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), C.c_uint32, C.c_uint32,
                                      C.c_uint32, P(AdaptiveParams), P(AccumulationBuffer), P(C.c_uint32), P(Stats)]),
+    "rt_robust_default_params": (C.c_int, [P(RobustParams)]),
+    "rt_robust_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rt_robust_combine_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, P(RobustParams),
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_robust_combine": (C.c_int, [C.c_int, P(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, P(RobustParams),
+                                    P(C.c_float), P(C.c_float)]),
+    "rt_render_robust_device": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
+                                          C.c_uint32, C.c_uint32, C.c_uint32, P(RobustParams), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, P(Stats)]),
+    "rt_render_robust": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
+                                   C.c_uint32, C.c_uint32, C.c_uint32, P(RobustParams), P(C.c_float), P(C.c_float),
+                                   P(Stats)]),
+    "rt_render_picture_robust": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
+                                           C.c_uint32, C.c_uint32, P(PostSettings), P(RobustParams),
+                                           P(DenoiseFeaturesParams), C.c_uint32, P(C.c_uint32), P(Stats)]),
 }
 
 HOST_FUNCTIONS = {

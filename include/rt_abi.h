@@ -660,6 +660,79 @@ int rt_render_adaptive(rt_scene* scene, const rt_camera* camera, const rt_settin
                        const rt_adaptive_params* p, rt_accumulation_buffer* accum, uint32_t* out_tile_spp,
                        rt_stats* stats);
 
+/* The robust estimator: a Gini-adaptive median of means (after Buisine, Delepoulle, Renaud, EGSR 2021) over a
+ * stack of accumulation buffers, per pixel, in place of the plain mean.  Beyond the reference, whose
+ * AccumulationBuffer is a mean: an opt-in of new entries only (no existing struct or entry changes;
+ * RT_ABI_VERSION stays).  DESIGN.md ("The robust estimator") defines it operation by operation; the device
+ * matches the plain-C restatement tests/ref_robust/ref_robust.c bit for bit.  In short, per pixel:
+ *   - the stack is `count` (2..32) buffers of w*h float4 (sum w*rgb, sum w) holding disjoint sample sets of one
+ *     frame, buffer k at float offset k*w*h*4 of one allocation;
+ *   - buffer k is valid when its weight is > 0.001f, its four floats are finite, m_k = S_k.xyz / S_k.w is
+ *     finite and key_k = (m_k.r + m_k.g) + m_k.b is finite; n = the number of valid buffers.  With n = 0 the
+ *     pixel is buffer 0's four floats unchanged (the output pass still shows NaN and negative weights);
+ *   - the valid buffers are ranked by ascending key (-0 as +0), equal keys by buffer index; their Gini
+ *     coefficient G in [0, 1) is taken over max(key, 0) (0 when n < 3 or the keys sum to nothing);
+ *   - c = min(floor(gini_scale * G * n/2), (n-1)/2, max_trim) buffers are dropped at each end of the ranking
+ *     and the rest pooled: {sum S_k.xyz / sum S_k.w, 1.0f}, added in buffer order.  c = 0 (gini_scale = 0, or
+ *     equal buffers) is the pooled mean of the valid buffers;
+ *   - info (optional, w*h float4) receives {G, (float)c, (float)n, sum S_k.w of the kept buffers}.
+ * The estimate trades energy for variance: it drops the rare bright samples of glass, and with them the part
+ * of the true radiance they carry (DESIGN.md has the measurements, losses included). */
+typedef struct rt_robust_params {
+    uint32_t buffers;      /* K of the drivers: 2..32; default 8 */
+    float    gini_scale;   /* >= 0, finite; 0 = pooled mean; default 1.0f */
+    uint32_t max_trim;     /* cap of c; default 15 (no cap beyond (n-1)/2) */
+    int32_t  reserved[5];
+} rt_robust_params;
+int    rt_robust_default_params(rt_robust_params* out);                          /* no device needed */
+size_t rt_robust_workspace_bytes(uint32_t w, uint32_t h, uint32_t buffers);      /* buffers*w*h*16; no device needed */
+/* The stage alone.  d_stack, d_out and d_info (may be NULL) are device pointers on `device`; d_out may be any
+ * buffer of the stack (a thread touches only its own pixel).  p->buffers is not read: `count` rules.
+ * `hip_stream` may be NULL; returns after the kernel has completed.  RT_ERROR_INVALID by name, before the
+ * device is touched: a NULL stack, parameter or output, w or h of 0, a count outside 2..32, a negative or
+ * non-finite gini_scale. */
+int rt_robust_combine_device(int device, const float* d_stack, uint32_t count, uint32_t w, uint32_t h,
+                             const rt_robust_params* p, float* d_out, float* d_info, void* hip_stream);
+/* Same, from and to host memory.  RT_ERROR_NO_DEVICE without a GPU (after the argument checks). */
+int rt_robust_combine(int device, const float* stack, uint32_t count, uint32_t w, uint32_t h,
+                      const rt_robust_params* p, float* out, float* info);
+/* The driver, written on the public entries.  K = p->buffers; settings->samples_per_pixel must be a positive
+ * multiple of K.  The stack (d_workspace: rt_robust_workspace_bytes(w, h, K) bytes; with NULL the call
+ * allocates and frees its own) is zeroed; buffer k is shard k of K of the frame by sample passes: rt_render_device
+ * with the caller's settings and frame_count, rt_tile_set {tile_w, tile_h, k, K} and the scene's shard mode set to
+ * RT_SHARD_PASSES for the call (rt_scene_set_config; put back on every way out), i.e. passes
+ * [k*spp/K, (k+1)*spp/K) of every tile.  Together the buffers are exactly the samples a uniform frame of
+ * samples_per_pixel draws at frame_count.  (A frame of spp/K samples at frame_count + k*spp/K is not: it takes
+ * the same canonical sample indices under other random streams, because a sample's seed hashes its frame's
+ * frame_count.)  A pass shard never takes the exact splat: the frames stream, as a rank's share does.  The
+ * caller's `tiles` must be unsharded (shard_index 0, shard_count 1).  Then rt_robust_combine_device writes d_out
+ * (w*h float4: overwritten, not added to, as the denoise stage's) and d_info (may be NULL).  The counters of
+ * `stats` are sums over the frames (those of the uniform frame), `seconds` the wall time of the whole call,
+ * splat_mode and shadow_launch the last frame's.  rt_cancel is read after every frame and ends the call with
+ * RT_ERROR_CANCELLED (d_out is then untouched).  RT_ERROR_INVALID by name before the device is touched: a NULL
+ * parameter, scene, camera, settings, filter, tiles or output; w or h of 0; buffers outside 2..32; a negative or
+ * non-finite gini_scale; samples_per_pixel of 0 or no multiple of buffers; sharded tiles.  A frame costs about
+ * 2.4 ms whatever it renders, K times here. */
+int rt_render_robust_device(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                            const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                            uint32_t w, uint32_t h, uint32_t frame_count, const rt_robust_params* p,
+                            void* d_workspace, float* d_out, float* d_info, void* hip_stream, rt_stats* stats);
+/* Same, into host memory (out w*h float4; info w*h float4 or NULL). */
+int rt_render_robust(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                     const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                     uint32_t w, uint32_t h, uint32_t frame_count, const rt_robust_params* p, float* out,
+                     float* info, rt_stats* stats);
+/* rt_render_picture with the robust estimator, written on the public entries: rt_render_robust_device at
+ * frame_count 0 into a fresh buffer; with `dp` (may be NULL) the three feature frames of guide_spp samples per
+ * pixel (0: settings->samples_per_pixel) by rt_render_features_device and rt_denoise_features_device on the
+ * robust output, as rt_render_picture_features_denoised does; rt_postprocess_device with the dither texture
+ * of total_frame_index + 1.  `stats` is the driver's. */
+int rt_render_picture_robust(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                             const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                             uint32_t w, uint32_t h, const rt_post_settings* post, const rt_robust_params* p,
+                             const rt_denoise_features_params* dp, uint32_t guide_spp, uint32_t* out_bgra,
+                             rt_stats* stats);
+
 /* The reference's top-down BVH builders on the device (RT/bvh.cpp:222-326 with
  * partition_midpoint :53-61, partition_sah_binned :138-213 or the full SAH sweep
  * partition_objects_sah / evaluate_sah :63-131, the partition of :26-51): one launch per
