@@ -250,6 +250,8 @@ ABI_FUNCTIONS = {
     "rt_debug_rank_slots": (C.c_int, [P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32)]),
     "rt_scene_ramp_stats": (C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64)]),
     "rt_debug_verify_rcp": (C.c_int, [C.c_int, P(C.c_uint64), P(C.c_uint32)]),
+    "rt_debug_verify_div_pi": (C.c_int, [C.c_int, P(C.c_uint64), P(C.c_uint32)]),
+    "rt_debug_verify_div3": (C.c_int, [C.c_int, C.c_uint32, P(C.c_float), P(C.c_uint64), P(C.c_uint32)]),
     "rt_set_profiling": (C.c_int, [C.c_int]),
     "rt_set_profiling_stages": (C.c_int, [C.c_uint32]),
     "rt_set_path_pool": (C.c_int, [C.c_uint32]),

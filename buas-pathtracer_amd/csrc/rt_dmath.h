@@ -58,6 +58,59 @@ RT_D float rcp_cr(float x) {
     return 1.0f / x;
 }
 RT_D V3 rcp3(V3 a) { return {rcp_cr(a.x), rcp_cr(a.y), rcp_cr(a.z)}; }
+// x / PI_32, correctly rounded, in 3 VALU: the quotient estimate x*c (c = fl(1/PI_32)) corrected once by
+// its FMA residual.  Whether one correction always lands on the rounded quotient depends on the
+// constant, so this holds for PI_32 only, by enumeration: rt_debug_verify_div_pi checks it against
+// the IEEE division for every one of the 2^32 floats (tests/test_gpu_div_helpers.py).  Valid for |x| in
+// [2^-100, FLT_MAX]: below, the residual (about 2^-23 |x|) leaves the normal range; -0 would come
+// out as +0; inf gives NaN.  Other inputs take the full division; a wave whose lanes are all in
+// range skips it, as in rcp_cr.
+struct ByPi {                                               // a verified divisor: D, C = fl(1 / D)
+    static constexpr float D = PI_32, C = 0x1.45f306p-2f;
+};
+static_assert(ByPi::C == 1.0f / ByPi::D, "ByPi::C is the rounded reciprocal of PI_32");
+template <class K>
+RT_D float div_const(float x) {
+    const float a = __builtin_fabsf(x);
+    if (a >= 0x1p-100f && a <= FLT_MAX_) {
+        const float q0 = x * K::C;
+        return __builtin_fmaf(__builtin_fmaf(-K::D, q0, x), K::C, q0);
+    }
+    return x / K::D;
+}
+RT_D float div_pi(float x) { return div_const<ByPi>(x); }
+// Three numerators over one denominator: the denominator's part of the division expansion (v_rcp_f32
+// and its two refinement FMAs) once, then per numerator exactly the expansion's FMA chain,
+//   q0 = n*r; e = fma(-d, q0, n); q1 = fma(e, r, q0); e = fma(-d, q1, n); q = fma(e, r, q1),
+// i.e. the expansion without v_div_scale_f32, v_div_fmas_f32's scaling and v_div_fixup_f32: 18 VALU
+// and the range test for 33.  The same operations in the same order give the same bits whenever those
+// three instructions do nothing.  By the ISA's definitions, with |n| and |d| both in [2^-46, 2^46]:
+//   v_div_scale_f32 scales (and sets VCC, which makes v_div_fmas_f32 scale back) when an operand is
+//     zero or denormal, 1/d is denormal (|d| > 2^126), n/d is denormal or exponent(n) - exponent(d)
+//     >= 96 (here |exponent difference| <= 93, so |n/d| in [2^-93, 2^93]), or the numerator's biased
+//     exponent is <= 23 (|n| < 2^-103): none of these;
+//   v_div_fixup_f32 replaces the quotient for a NaN, infinite or zero operand and for an exponent
+//     difference beyond +-150 or so, and otherwise returns |q| with the sign of n xor d, which a
+//     non-zero q already has.
+// Anything else (zeros, NaN, inf included: every comparison with NaN is false) takes the plain
+// divisions, per lane; a wave whose lanes are all in range skips them.  rt_debug_verify_div3 compares
+// the two forms bitwise on the device (tests/test_gpu_div_helpers.py).
+constexpr float DIV3_LO = 0x1p-46f, DIV3_HI = 0x1p46f;
+RT_D bool div3_in_range(float x) { const float a = __builtin_fabsf(x); return a >= DIV3_LO && a <= DIV3_HI; }
+RT_D V3 div3_by(V3 n, float d) {
+#ifndef RT_DMATH_HOST_TEST
+    if (div3_in_range(d) && div3_in_range(n.x) && div3_in_range(n.y) && div3_in_range(n.z)) {
+        const float r0 = __builtin_amdgcn_rcpf(d);
+        const float r = __builtin_fmaf(__builtin_fmaf(-d, r0, 1.0f), r0, r0);
+        V3 q = {n.x * r, n.y * r, n.z * r};
+        q = {__builtin_fmaf(__builtin_fmaf(-d, q.x, n.x), r, q.x), __builtin_fmaf(__builtin_fmaf(-d, q.y, n.y), r, q.y),
+             __builtin_fmaf(__builtin_fmaf(-d, q.z, n.z), r, q.z)};
+        return {__builtin_fmaf(__builtin_fmaf(-d, q.x, n.x), r, q.x), __builtin_fmaf(__builtin_fmaf(-d, q.y, n.y), r, q.y),
+                __builtin_fmaf(__builtin_fmaf(-d, q.z, n.z), r, q.z)};
+    }
+#endif
+    return {n.x / d, n.y / d, n.z / d};
+}
 RT_D float dot(V3 a, V3 b) { return a.x*b.x + a.y*b.y + a.z*b.z; }
 RT_D V3 cross(V3 a, V3 b) { return {a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x}; }
 RT_D float length_sq(V3 a) { return dot(a, a); }

@@ -144,12 +144,18 @@ RT_D DevScene scene_in_lds(const DevScene& sc, float4* lds) {
 
 struct Ray { V3 o, d, inv_d; uint32_t neg; float max_t; uint32_t zero; };   // zero: axes with d == 0
 
-RT_D Ray make_ray(V3 o, V3 d, float far_clip) {              // RT/intersection.h:13-24
+// a ray without its inv_d (the caller sets it: a reciprocal it already holds, or rcp3(d)); far clip 0
+RT_D Ray make_ray_dir(V3 o, V3 d) {
     Ray r;
     r.o = o; r.d = d;
-    r.inv_d = rcp3(d);
     r.neg = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
     r.zero = (d.x == 0.0f ? 1u : 0u) | (d.y == 0.0f ? 2u : 0u) | (d.z == 0.0f ? 4u : 0u);
+    r.max_t = 0.0f;
+    return r;
+}
+RT_D Ray make_ray(V3 o, V3 d, float far_clip) {              // RT/intersection.h:13-24
+    Ray r = make_ray_dir(o, d);
+    r.inv_d = rcp3(d);
     r.max_t = far_clip;
     return r;
 }
@@ -317,7 +323,7 @@ RT_D void unpack_node(const rt_bvh_node* nodes, uint32_t x, uint32_t& lf, uint32
 //   mesh:       q3.zw = node_off, tri_off; q4 = root record, root bv_p.xyz; q5 = root bv_r.xyz
 constexpr int LEAF_REC_Q = 6;
 // q3.y: the primitive type in bits 0-7; LEAF_TRANSLATE: the inverse's 3x3 part is
-// exactly the identity and its translation finite (spheres and unrotated boxes)
+// exactly the identity and its translation finite (spheres, unrotated boxes and mesh instances)
 constexpr uint32_t LEAF_TRANSLATE = 0x100u;
 
 // transform_ray (RT/intersection.cpp:403-409) into a leaf record's object space.  For a
@@ -548,7 +554,13 @@ RT_D Prologue ray_prologue(const DevScene& sc, V3 o, V3 d, float max_t, bool occ
                 Ray ir; ir.o = io; ir.d = id;
                 hit = ray_sphere(ir, q3.z, r.t);
             } else {
-                const Ray ir = make_ray(io, id, 0.0f);
+                // a translate-only leaf leaves a plain ray's direction as it is (object_ray: id = d), so
+                // its 1/d is the world ray's, bit for bit.  Where every lane here is such a ray the
+                // three reciprocals are not redone; otherwise all lanes redo them (the same bits for
+                // the lanes that could have kept theirs).
+                Ray ir = make_ray_dir(io, id);
+                if (__ballot(!((tword & LEAF_TRANSLATE) && plain)) == 0ull) ir.inv_d = wr.inv_d;
+                else ir.inv_d = rcp3(id);
                 if (type == RT_PRIMITIVE_MESH) {                   // the mesh root's pop-time test (:269-275)
                     const f32x8 qb = ld_uniform_v<f32x8>(q + 4);
                     const float4 q4 = q4_of(qb, 0), q5 = q4_of(qb, 1);
@@ -781,6 +793,30 @@ struct Traversal {
         h[1] = bv_static<FIN>(r, {F[0].y, F[1].y, F[2].y}, {F[3].y, F[4].y, F[5].y}, tn[1]) && rec[1] != EMPTY4;
         h[2] = bv_static<FIN>(r, {F[0].z, F[1].z, F[2].z}, {F[3].z, F[4].z, F[5].z}, tn[2]) && rec[2] != EMPTY4;
         h[3] = bv_static<FIN>(r, {F[0].w, F[1].w, F[2].w}, {F[3].w, F[4].w, F[5].w}, tn[3]) && rec[3] != EMPTY4;
+        if (!REF) {
+            // Each child goes to the level it has once all four are pushed: sp + the hit children visited
+            // after it -- its pair's other child when that one comes second, and the other pair when
+            // this pair is visited first.  The same entries at the same levels as pushing them one by
+            // one in reverse visit order (the REF form below); an entry past the 64-entry limit is
+            // dropped, as there (the sequential form drops the last ones it pushes: the highest levels).
+            uint32_t b0 = h[0] ? 1u : 0u, b1 = h[1] ? 1u : 0u, b2 = h[2] ? 1u : 0u, b3 = h[3] ? 1u : 0u;
+#ifdef __HIP_DEVICE_COMPILE__
+            // the flags from here on as lane values: four lane masks held to the stores cost the merged
+            // trace kernel an SGPR spill (and the VGPR that holds it)
+            asm volatile("" : "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3));
+#endif
+            const uint32_t nl = b0 + b1, nr = b2 + b3;
+            const uint32_t ol = g ? 0u : nr, orr = g ? nl : 0u;    // the other pair comes later
+            const int l0 = sp + (int)(ol + (fa ? 0u : b1)), l1 = sp + (int)(ol + (fa ? b0 : 0u));
+            const int l2 = sp + (int)(orr + (fb ? 0u : b3)), l3 = sp + (int)(orr + (fb ? b2 : 0u));
+            if (b0 && (SH || l0 < STACK_DEPTH)) st.template put<SH>(l0, rec[0], tn[0]);
+            if (b1 && (SH || l1 < STACK_DEPTH)) st.template put<SH>(l1, rec[1], tn[1]);
+            if (b2 && (SH || l2 < STACK_DEPTH)) st.template put<SH>(l2, rec[2], tn[2]);
+            if (b3 && (SH || l3 < STACK_DEPTH)) st.template put<SH>(l3, rec[3], tn[3]);
+            sp += (int)(nl + nr);
+            if (!SH && sp > STACK_DEPTH) sp = STACK_DEPTH;
+            return;
+        }
         // visit order: first pair (2g + its first, 2g + its second), then the other pair; push reversed
         const uint32_t f1 = g ? fb : fa, f2 = g ? fa : fb;
         const uint32_t v[4] = {2u*g + f1, 2u*g + 1u - f1, 2u*(1u - g) + f2, 2u*(1u - g) + 1u - f2};
@@ -2189,7 +2225,7 @@ RT_D bool shade_bounce(const DevScene& sc, const rt_settings& st, const SamplerS
                             V3 Le = sky_env(sc, Lv, tile);
                             float pe = env_pdf(sc, tile, Lv);
                             if (pe > 0.0f) {
-                                float bpdf = (st.importance_sample_diffuse ? ndl / PI_32 : 1.0f / (2.0f*PI_32));
+                                float bpdf = (st.importance_sample_diffuse ? div_pi(ndl) : 1.0f / (2.0f*PI_32));
                                 float pdf = st.use_mis ? q*pe + bpdf : q*pe;
                                 sh_c = mul(mul(muls(thr, ndl / pdf), brdf), Le);
                                 sh_o = add(I, muls(Lv, EPSILON));
@@ -2211,7 +2247,7 @@ RT_D bool shade_bounce(const DevScene& sc, const rt_settings& st, const SamplerS
                             V3 Lv = sub(pw, I);
                             float dsq = length_sq(Lv);
                             float dist = __builtin_sqrtf(dsq);
-                            Lv = divs(Lv, dist);
+                            Lv = div3_by(Lv, dist);
                             float A = 2.0f*PI_32*rad*rad;
                             float ndl = dot(N, Lv);
                             float nndl = -dot(Nl, Lv);
@@ -2220,7 +2256,7 @@ RT_D bool shade_bounce(const DevScene& sc, const rt_settings& st, const SamplerS
                                 float pdf;
                                 if (st.use_mis) {
                                     float lpdf = rcp_cr(sa);
-                                    float bpdf = (st.importance_sample_diffuse ? ndl / PI_32 : 1.0f / (2.0f*PI_32));
+                                    float bpdf = (st.importance_sample_diffuse ? div_pi(ndl) : 1.0f / (2.0f*PI_32));
                                     pdf = lpdf + bpdf;
                                 } else {
                                     pdf = rcp_cr(sa);
@@ -2257,7 +2293,7 @@ RT_D bool shade_bounce(const DevScene& sc, const rt_settings& st, const SamplerS
             }
         }
         if (!done) {
-            if (st.importance_sample_diffuse) prev_pdf = dot(N, rd) / PI_32;   // prev_N = N, and the new ray
+            if (st.importance_sample_diffuse) prev_pdf = div_pi(dot(N, rd));   // prev_N = N, and the new ray
             ++bounce;
             if (bounce >= st.max_bounce_count) done = true;
         }
@@ -3153,7 +3189,7 @@ __global__ void __launch_bounds__(DTB) k_recurse(DevScene sc, rt_settings st, Fr
                         V3 Lv = sub(pw, I);
                         const float dsq = length_sq(Lv);
                         const float dist = __builtin_sqrtf(dsq);
-                        Lv = divs(Lv, dist);
+                        Lv = div3_by(Lv, dist);
                         const float A = 2.0f*PI_32*rad*rad;
                         const float ndl = dot(N, Lv);
                         const float nndl = -dot(Nl, Lv);
@@ -3820,6 +3856,33 @@ __global__ void __launch_bounds__(256) k_verify_rcp(uint32_t base, unsigned long
             atomicAdd(out, 1ull);
             atomicMin(out + 1, (unsigned long long)bits);
         }
+    }
+}
+
+// rt_debug_verify_div_pi: div_const<ByPi> against the IEEE division by PI_32, 16 inputs per thread.
+__global__ void __launch_bounds__(256) k_verify_div_pi(uint32_t base, unsigned long long* out) {
+    const uint32_t t = blockIdx.x*256 + threadIdx.x, stride = gridDim.x*256;
+    for (uint32_t i = 0; i < 16; ++i) {
+        const uint32_t bits = base + t + i*stride;
+        const float x = __uint_as_float(bits);
+        const float a = div_const<ByPi>(x), b = x / PI_32;
+        if (__float_as_uint(a) != __float_as_uint(b) && !(a != a && b != b)) {
+            atomicAdd(out, 1ull);
+            atomicMin(out + 1, (unsigned long long)bits);
+        }
+    }
+}
+// rt_debug_verify_div3: div3_by against three plain divisions, one (numerators, denominator) set per thread.
+__global__ void __launch_bounds__(256) k_verify_div3(const float4* sets, uint32_t count, unsigned long long* out) {
+    const uint32_t i = blockIdx.x*256 + threadIdx.x;
+    if (i >= count) return;
+    const float4 s = sets[i];
+    const V3 a = div3_by({s.x, s.y, s.z}, s.w);
+    const V3 b = {s.x / s.w, s.y / s.w, s.z / s.w};
+    auto differ = [](float p, float q) { return __float_as_uint(p) != __float_as_uint(q) && !(p != p && q != q); };
+    if (differ(a.x, b.x) || differ(a.y, b.y) || differ(a.z, b.z)) {
+        atomicAdd(out, 1ull);
+        atomicMin(out + 1, (unsigned long long)i);
     }
 }
 
@@ -5256,12 +5319,16 @@ int rt_scene_upload(const rt_scene_desc* d, int device, rt_scene** out) {
             float4* q = rec.data() + (size_t)j*LEAF_REC_Q;
             const M34& iv = inv[p.transform_index];
             for (int r = 0; r < 3; ++r) q[r] = make_float4(iv.e[r][0], iv.e[r][1], iv.e[r][2], iv.e[r][3]);
+            bool translate = std::isfinite(iv.e[0][3]) && std::isfinite(iv.e[1][3]) && std::isfinite(iv.e[2][3]);
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 3; ++c) translate = translate && iv.e[r][c] == (r == c ? 1.0f : 0.0f);
+            const uint32_t tword = p.type | (translate ? LEAF_TRANSLATE : 0u);
             if (p.type == RT_PRIMITIVE_MESH) {
                 const rt_mesh& M = d->meshes[p.mesh_index];
                 rt_bvh_node rn = {};
                 if (M.node_count) rn = M.nodes[0];
                 const uint32_t root = root4[p.mesh_index];
-                q[3] = make_float4(u2f(pi), u2f(p.type), u2f(meshes[p.mesh_index].node_offset), u2f(meshes[p.mesh_index].tri_offset));
+                q[3] = make_float4(u2f(pi), u2f(tword), u2f(meshes[p.mesh_index].node_offset), u2f(meshes[p.mesh_index].tri_offset));
                 q[4] = make_float4(u2f(root), rn.bv_p.x, rn.bv_p.y, rn.bv_p.z);
                 // q5.w: the mesh has a BVH.  Without one the reference tests none of its triangles
                 // (intersect_mesh, RT/intersection.cpp:259: `if (bvh)`): the root box is made empty
@@ -5269,10 +5336,7 @@ int rt_scene_upload(const rt_scene_desc* d, int device, rt_scene** out) {
                 if (M.node_count) q[5] = make_float4(rn.bv_r.x, rn.bv_r.y, rn.bv_r.z, 1.0f);
                 else q[5] = make_float4(-1.0f, -1.0f, -1.0f, 0.0f);
             } else {
-                bool translate = std::isfinite(iv.e[0][3]) && std::isfinite(iv.e[1][3]) && std::isfinite(iv.e[2][3]);
-                for (int r = 0; r < 3; ++r)
-                    for (int c = 0; c < 3; ++c) translate = translate && iv.e[r][c] == (r == c ? 1.0f : 0.0f);
-                q[3] = make_float4(u2f(pi), u2f(p.type | (translate ? LEAF_TRANSLATE : 0u)), p.p[0], p.p[1]);
+                q[3] = make_float4(u2f(pi), u2f(tword), p.p[0], p.p[1]);
                 q[4] = make_float4(p.p[2], 0.0f, 0.0f, 0.0f);
             }
         }
@@ -6181,6 +6245,49 @@ int rt_debug_verify_rcp(int device, uint64_t* out_mismatches, uint32_t* out_firs
     (void)hipFree(d);
     *out_mismatches = h[0];
     *out_first_bits = (uint32_t)h[1];
+    return RT_OK;
+}
+
+int rt_debug_verify_div_pi(int device, uint64_t* out_mismatches, uint32_t* out_first_bits) {
+    if (!out_mismatches || !out_first_bits) { set_error("null argument"); return RT_ERROR_INVALID; }
+    int err = bind_device(device);
+    if (err) return err;
+    unsigned long long* d = nullptr;
+    HIP_OK(hipMalloc(&d, 2*sizeof(unsigned long long)));
+    const unsigned long long init[2] = {0ull, 0xFFFFFFFFull};
+    HIP_OK(hipMemcpy(d, init, sizeof(init), hipMemcpyHostToDevice));
+    for (uint32_t chunk = 0; chunk < 16; ++chunk)                 // 2^28 inputs per launch
+        k_verify_div_pi<<<(1u << 28) / (256*16), 256>>>(chunk << 28, d);
+    HIP_OK(hipGetLastError());
+    unsigned long long h[2];
+    HIP_OK(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
+    (void)hipFree(d);
+    *out_mismatches = h[0];
+    *out_first_bits = (uint32_t)h[1];
+    return RT_OK;
+}
+
+int rt_debug_verify_div3(int device, uint32_t count, const float* sets, uint64_t* out_mismatches, uint32_t* out_first_index) {
+    if (!sets || !out_mismatches || !out_first_index) { set_error("null argument"); return RT_ERROR_INVALID; }
+    *out_mismatches = 0; *out_first_index = 0xFFFFFFFFu;
+    if (!count) return RT_OK;
+    int err = bind_device(device);
+    if (err) return err;
+    float4* d_s = nullptr;
+    unsigned long long* d = nullptr;
+    HIP_OK(hipMalloc(&d_s, sizeof(float4)*(size_t)count));
+    HIP_OK(hipMalloc(&d, 2*sizeof(unsigned long long)));
+    const unsigned long long init[2] = {0ull, 0xFFFFFFFFull};
+    HIP_OK(hipMemcpy(d, init, sizeof(init), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_s, sets, sizeof(float4)*(size_t)count, hipMemcpyHostToDevice));
+    k_verify_div3<<<(count + 255) / 256, 256>>>(d_s, count, d);
+    HIP_OK(hipGetLastError());
+    unsigned long long h[2];
+    HIP_OK(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
+    (void)hipFree(d_s);
+    (void)hipFree(d);
+    *out_mismatches = h[0];
+    *out_first_index = (uint32_t)h[1];
     return RT_OK;
 }
 

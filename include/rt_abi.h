@@ -416,6 +416,19 @@ int rt_scene_ramp_stats(const rt_scene* scene, uint64_t* out_iterations, uint64_
  * mismatching inputs and the smallest mismatching bit pattern (0xFFFFFFFF: none). */
 int rt_debug_verify_rcp(int device, uint64_t* out_mismatches, uint32_t* out_first_bits);
 
+/* The same for the kernels' division by the constant PI (3 instructions: an estimate
+ * and one residual correction) against the IEEE x / 3.14159265359f: every one of the
+ * 2^32 bit patterns. */
+int rt_debug_verify_div_pi(int device, uint64_t* out_mismatches, uint32_t* out_first_bits);
+
+/* The kernels' division of three numerators by one denominator (the division
+ * expansion with the denominator's part done once) against three IEEE divisions, bitwise
+ * (NaNs compare equal as NaNs), for `count` sets of 4 floats: numerators x, y, z and the
+ * denominator.  Writes the number of mismatching sets and the index of the first
+ * (0xFFFFFFFF: none). */
+int rt_debug_verify_div3(int device, uint32_t count, const float* sets, uint64_t* out_mismatches,
+                         uint32_t* out_first_index);
+
 /* The output pass of RT/raytracer.cpp:2103-2171 on the device: per pixel resolve
  * (xyz / w), exposure, 1-exp(-x) tonemap, sRGB power, sigmoidal contrast, x255,
  * TPDF dither from the reference's LDR_RGB1 blue-noise texture number
