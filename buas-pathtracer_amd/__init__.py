@@ -23,7 +23,7 @@ import numpy as np
 from . import abi
 from .abi import (V3, v3, M4x4Inv, Material, Camera, Settings, FilterCache, PostSettings, TileSet, Stats,
                   AccumulationBuffer, RayQuery, HitRecord, BvhInfo, DenoiseParams, DenoiseFeaturesParams,
-                  TileErrorParams, AdaptiveParams, RobustParams)
+                  TileErrorParams, AdaptiveParams, RobustParams, GBufferTexel, TemporalParams, TemporalState)
 
 __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settings", "load_reconstruction_kernel",
            "translate", "scale", "rotate_x", "rotate_y", "rotate_z", "identity", "aim_camera", "aim_camera_at",
@@ -33,7 +33,8 @@ __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settin
            "denoise_workspace_bytes", "DenoiseFeaturesParams", "default_denoise_features_params", "denoise_features",
            "denoise_features_workspace_bytes", "TileErrorParams", "AdaptiveParams", "default_tile_error_params",
            "default_adaptive_params", "adaptive_workspace_bytes", "tile_error", "RobustParams", "default_robust_params",
-           "robust_workspace_bytes", "robust_combine"]
+           "robust_workspace_bytes", "robust_combine", "GBufferTexel", "TemporalParams", "TemporalState",
+           "default_temporal_params", "temporal_workspace_bytes", "temporal_accumulate", "temporal_accumulate_device"]
 
 PI_32 = 3.14159265359
 DEG_TO_RAD = 6.28318530717 / 360.0
@@ -544,6 +545,50 @@ class DeviceScene:
                                               out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(stats)))
         return out, stats
 
+    def gbuffer(self, camera, w, h, lens_distortion=0.0):
+        """rt_gbuffer: the primary hit of every pixel's jitter-free pinhole ray -> a structured array (h, w) of
+        abi.GBUFFER_DTYPE {p, t, n, primitive}; a miss is {the ray's direction, 0, 0, RT_HIT_MISS}."""
+        out = np.zeros((h, w), abi.GBUFFER_DTYPE)
+        _check(lib().rt_gbuffer(self._h, C.byref(camera), float(lens_distortion), w, h,
+                                out.ctypes.data_as(C.POINTER(GBufferTexel))))
+        return out
+
+    def gbuffer_device(self, camera, w, h, d_out, lens_distortion=0.0, stream=None):
+        """rt_gbuffer_device into a device pointer of w*h 32-byte texels (e.g. a torch tensor's .data_ptr())."""
+        _check(lib().rt_gbuffer_device(self._h, C.byref(camera), float(lens_distortion), w, h, C.c_void_p(d_out),
+                                       C.c_void_p(stream) if stream else None))
+
+    def render_temporal(self, camera, settings, filter_cache, w, h, state, params=None, frame_count=0, total_frame_index=0,
+                        tile=64, shard_index=0, shard_count=1, want_length=True):
+        """rt_render_temporal: one frame of the loop.  `state` is a TemporalState whose d_workspace points at
+        temporal_workspace_bytes(w, h) bytes on the device (all else zero at the start); it is updated in place
+        -> (history float32 [h,w,4] = {r, g, b, 1}, length float32 [h,w] or None, the beauty frame's stats)."""
+        if params is None:
+            params = default_temporal_params()
+        out = np.zeros((h, w, 4), np.float32)
+        length = np.zeros((h, w), np.float32) if want_length else None
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        fp = C.POINTER(C.c_float)
+        _check(lib().rt_render_temporal(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache), C.byref(tiles),
+                                        total_frame_index, w, h, frame_count, C.byref(params), C.byref(state),
+                                        out.ctypes.data_as(fp), length.ctypes.data_as(fp) if want_length else None,
+                                        C.byref(stats)))
+        return out, length, stats
+
+    def render_temporal_device(self, camera, settings, filter_cache, w, h, params, state, d_out, d_length_out=None,
+                               stream=None, frame_count=0, total_frame_index=0, tile=64, shard_index=0, shard_count=1):
+        """rt_render_temporal_device into device pointers (d_out w*h float4, d_length_out w*h floats or None; both
+        overwritten); `state` as for render_temporal -> the beauty frame's stats."""
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        _check(lib().rt_render_temporal_device(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                               C.byref(tiles), total_frame_index, w, h, frame_count, C.byref(params),
+                                               C.byref(state), C.c_void_p(d_out),
+                                               C.c_void_p(d_length_out) if d_length_out else None,
+                                               C.c_void_p(stream) if stream else None, C.byref(stats)))
+        return stats
+
     def configure(self, **fields):
         """rt_scene_set_config with the named fields changed, e.g. configure(partitions=1,
         splat_mode=abi.RT_SPLAT_EXACT).  Returns the previous configuration (pass it to
@@ -738,6 +783,56 @@ def robust_combine(stack, params=None, device=0, want_info=True):
     _check(lib().rt_robust_combine(device, stack.ctypes.data_as(fp), k, w, h, C.byref(params), out.ctypes.data_as(fp),
                                    info.ctypes.data_as(fp) if want_info else None))
     return out, info
+
+
+def default_temporal_params():
+    """rt_temporal_default_params (no device needed) -> TemporalParams."""
+    p = TemporalParams()
+    _check(lib().rt_temporal_default_params(C.byref(p)))
+    return p
+
+
+def temporal_workspace_bytes(w, h):
+    """rt_temporal_workspace_bytes (no device needed): the driver's workspace, 120 bytes per pixel."""
+    return int(lib().rt_temporal_workspace_bytes(w, h))
+
+
+def temporal_accumulate(current, gbuffer, prev=None, prev_camera=None, prev_lens_distortion=0.0, params=None, device=0):
+    """The accumulate stage on the GPU (rt_temporal_accumulate): a host accumulation buffer (h, w, 4), its G-buffer
+    (h, w) of abi.GBUFFER_DTYPE and, with history, prev = (history (h, w, 4), length (h, w), gbuffer (h, w)) of the
+    frame before with its camera and lens distortion -> (history (h, w, 4), length (h, w))."""
+    current = np.ascontiguousarray(current, np.float32)
+    h, w, _ = current.shape
+    gbuffer = np.ascontiguousarray(gbuffer, abi.GBUFFER_DTYPE)
+    assert gbuffer.shape == (h, w)
+    if params is None:
+        params = default_temporal_params()
+    fp, gp = C.POINTER(C.c_float), C.POINTER(GBufferTexel)
+    ph = pl = pg = None
+    if prev is not None:
+        ph = np.ascontiguousarray(prev[0], np.float32)
+        pl = np.ascontiguousarray(prev[1], np.float32)
+        pg = np.ascontiguousarray(prev[2], abi.GBUFFER_DTYPE)
+        assert ph.shape == (h, w, 4) and pl.shape == (h, w) and pg.shape == (h, w)
+    history = np.zeros((h, w, 4), np.float32)
+    length = np.zeros((h, w), np.float32)
+    _check(lib().rt_temporal_accumulate(device, current.ctypes.data_as(fp), gbuffer.ctypes.data_as(gp),
+                                        None if ph is None else ph.ctypes.data_as(fp),
+                                        None if pl is None else pl.ctypes.data_as(fp),
+                                        None if pg is None else pg.ctypes.data_as(gp),
+                                        None if prev_camera is None else C.byref(prev_camera), float(prev_lens_distortion),
+                                        w, h, C.byref(params), history.ctypes.data_as(fp), length.ctypes.data_as(fp)))
+    return history, length
+
+
+def temporal_accumulate_device(d_current, d_gbuffer, d_prev_history, d_prev_length, d_prev_gbuffer, prev_camera,
+                               prev_lens_distortion, w, h, params, d_history, d_length, device=0, stream=None):
+    """rt_temporal_accumulate_device on device pointers (the three d_prev_* all None for no history)."""
+    vp = lambda a: C.c_void_p(a) if a else None
+    _check(lib().rt_temporal_accumulate_device(device, vp(d_current), vp(d_gbuffer), vp(d_prev_history), vp(d_prev_length),
+                                               vp(d_prev_gbuffer), None if prev_camera is None else C.byref(prev_camera),
+                                               float(prev_lens_distortion), w, h, C.byref(params), vp(d_history),
+                                               vp(d_length), vp(stream)))
 
 
 def write_bitmap(path, bgra):

@@ -214,6 +214,24 @@ class RobustParams(C.Structure):       # rt_robust_params (the robust estimator:
     _fields_ = [("buffers", C.c_uint32), ("gini_scale", C.c_float), ("max_trim", C.c_uint32), ("reserved", C.c_int32 * 5)]
 
 
+class GBufferTexel(C.Structure):       # rt_gbuffer_texel (temporal accumulation: the primary hit of a pixel), 32 bytes
+    _fields_ = [("p", V3), ("t", C.c_float), ("n", V3), ("primitive", C.c_uint32)]
+
+
+# the numpy layout of a G-buffer: np.zeros((h, w), GBUFFER_DTYPE)
+GBUFFER_DTYPE = [("p", "<f4", (3,)), ("t", "<f4"), ("n", "<f4", (3,)), ("primitive", "<u4")]
+
+
+class TemporalParams(C.Structure):     # rt_temporal_params (temporal accumulation: the accumulate stage)
+    _fields_ = [("max_history", C.c_float), ("normal_cos", C.c_float), ("plane_tolerance", C.c_float),
+                ("snap", C.c_float), ("firefly_clamp", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class TemporalState(C.Structure):      # rt_temporal_state (temporal accumulation: the driver's; all zero = no history)
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("frames", C.c_uint32), ("parity", C.c_uint32),
+                ("camera", Camera), ("lens_distortion", C.c_float), ("d_workspace", C.c_void_p)]
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("node_count", C.c_uint32), ("leaf_count", C.c_uint32), ("max_depth", C.c_uint32),
                 ("max_leaf_size", C.c_uint32)]
@@ -330,6 +348,22 @@ ABI_FUNCTIONS = {
     "rt_render_picture_robust": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
                                            C.c_uint32, C.c_uint32, P(PostSettings), P(RobustParams),
                                            P(DenoiseFeaturesParams), C.c_uint32, P(C.c_uint32), P(Stats)]),
+    "rt_gbuffer_device": (C.c_int, [C.c_void_p, P(Camera), C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_gbuffer": (C.c_int, [C.c_void_p, P(Camera), C.c_float, C.c_uint32, C.c_uint32, P(GBufferTexel)]),
+    "rt_temporal_default_params": (C.c_int, [P(TemporalParams)]),
+    "rt_temporal_accumulate_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                P(Camera), C.c_float, C.c_uint32, C.c_uint32, P(TemporalParams),
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_temporal_accumulate": (C.c_int, [C.c_int, P(C.c_float), P(GBufferTexel), P(C.c_float), P(C.c_float),
+                                         P(GBufferTexel), P(Camera), C.c_float, C.c_uint32, C.c_uint32,
+                                         P(TemporalParams), P(C.c_float), P(C.c_float)]),
+    "rt_temporal_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rt_render_temporal_device": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams), P(TemporalState),
+                                            C.c_void_p, C.c_void_p, C.c_void_p, P(Stats)]),
+    "rt_render_temporal": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
+                                     C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams), P(TemporalState),
+                                     P(C.c_float), P(C.c_float), P(Stats)]),
 }
 
 HOST_FUNCTIONS = {

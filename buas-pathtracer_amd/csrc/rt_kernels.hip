@@ -3822,6 +3822,56 @@ __global__ void __launch_bounds__(128) k_debug_intersect(DevScene sc, const rt_r
     out[i] = r;
 }
 
+// k_gbuffer — the primary-hit G-buffer of temporal accumulation (rt_gbuffer_device; DESIGN.md "Temporal
+// accumulation").  render_tile's camera ray (RT/raytracer.cpp:397-460) in k_generate's expression order, without
+// jitter and lens offset, through the same Traversal step machine; the texel is k_debug_intersect<false>'s record.
+// A fixed grid strides over the pixels, so the spill area is sized by the grid (rt_scene::gbuf_spill), not the frame.
+struct GbufParams {
+    V3 cp, cx, cy, cz;
+    float focus_distance, film_distance, half_film_w, half_film_h, lens_distortion;
+    uint32_t w, h;
+};
+constexpr int GB_BLOCK = 128;
+constexpr uint32_t GB_MAX_GRID = 1024;  // 4 blocks a CU; (STACK_DEPTH - STACK_LDS)*8 B*GB_BLOCK*GB_MAX_GRID = 48 MiB of spill
+__global__ void __launch_bounds__(GB_BLOCK) k_gbuffer(DevScene sc, GbufParams gp, rt_gbuffer_texel* out, uint2* spill) {
+    __shared__ uint2 lds_stack[STACK_LDS*GB_BLOCK];
+    __shared__ float2 lds_bary[GB_BLOCK];
+    Stack st;
+    st.lds = lds_stack; st.spill = spill; st.bary = lds_bary; st.lane = threadIdx.x; st.block = GB_BLOCK;
+    st.gtid = blockIdx.x*GB_BLOCK + threadIdx.x; st.nthreads = gridDim.x*GB_BLOCK;
+    const uint32_t n = gp.w*gp.h;
+    // camera (RT/raytracer.cpp:381-401)
+    const float hfw = gp.half_film_w*gp.focus_distance;
+    const float hfh = gp.half_film_h*gp.focus_distance;
+    const float film_distance = gp.focus_distance*gp.film_distance;
+    const V3 film_center = sub(gp.cp, smul(film_distance, gp.cz));
+    const float pixel_w = 1.0f / (float)gp.w, pixel_h = 1.0f / (float)gp.h;
+    for (uint64_t i = st.gtid; i < n; i += st.nthreads) {             // 64 bits: i + nthreads may pass 2^32
+        const uint32_t y = (uint32_t)i / gp.w, x = (uint32_t)i - y*gp.w;
+        float v = 1.0f - 2.0f*(float)y*pixel_h;
+        float u = 1.0f - 2.0f*(float)x*pixel_w;
+        apply_lens_distortion(gp.lens_distortion, gp.w, gp.h, u, v);
+        V3 film_p = film_center;
+        film_p = add(film_p, smul(u*hfw, gp.cx));
+        film_p = add(film_p, smul(v*hfh, gp.cy));
+        const V3 rd = normalize(sub(film_p, gp.cp));
+        Traversal<false> tr;
+        tr.init(sc, st, gp.cp, rd, FLT_MAX_, 0u);
+        while (tr.mode != TM_DONE && tr.step(sc, st)) {}
+        const Hit h = tr.result(st);
+        rt_gbuffer_texel g;
+        if (h.code != RT_HIT_MISS) {
+            Ray ray = make_ray(gp.cp, rd, FLT_MAX_);
+            V3 I, N; uint32_t mid;
+            hit_geometry(sc, ray, h, I, N, mid);
+            g.p = {I.x, I.y, I.z}; g.t = h.t; g.n = {N.x, N.y, N.z}; g.primitive = h.code;
+        } else {
+            g.p = {rd.x, rd.y, rd.z}; g.t = 0.0f; g.n = {0.0f, 0.0f, 0.0f}; g.primitive = RT_HIT_MISS;
+        }
+        out[i] = g;
+    }
+}
+
 // k_post — the output pass (RT/raytracer.cpp:2103-2171): resolve, exposure,
 // tonemap, sRGB, contrast, TPDF dither, BGRA8.  One pixel per thread; 16 B in,
 // 4 B out (HBM-bound).  The dither texture (196 KB) stays in L2.
@@ -4004,6 +4054,7 @@ struct rt_scene {
     float4* frames = nullptr;
     uint32_t recurse_grid = 0;          // persistent k_recurse blocks (<= trace_grid*TB/DTB: the spill area)
     V3 ambient = {0, 0, 0};             // Scene::ambient_light (RT/scene.h:102), read by Whitted only
+    uint2* gbuf_spill = nullptr;        // k_gbuffer's traversal spill area (GB_MAX_GRID blocks), from the first rt_gbuffer_device on
 };
 
 namespace {
@@ -5498,6 +5549,7 @@ int rt_scene_free(rt_scene* s) {
     if (s->d_partials) (void)hipFree(s->d_partials);
     if (s->d_aux) (void)hipFree(s->d_aux);
     if (s->frames) (void)hipFree(s->frames);
+    if (s->gbuf_spill) (void)hipFree(s->gbuf_spill);
     delete s;
     return RT_OK;
 }
@@ -6310,6 +6362,60 @@ int rt_debug_intersect(rt_scene* s, uint32_t count, const rt_ray_query* rays, in
     HIP_OK(hipMemcpy(out, d_o, sizeof(rt_hit_record)*count, hipMemcpyDeviceToHost));
     (void)hipFree(d_r); (void)hipFree(d_o);
     return RT_OK;
+}
+
+namespace {
+int check_gbuffer(const char* entry, const rt_scene* s, const rt_camera* camera, uint32_t w, uint32_t h, const void* out,
+                  const char* out_name) {
+    const std::string e = entry;
+    if (!camera) { set_error(e + ": null camera"); return RT_ERROR_INVALID; }
+    if (!out) { set_error(e + ": null " + out_name); return RT_ERROR_INVALID; }
+    if (!w) { set_error(e + ": w is 0"); return RT_ERROR_INVALID; }
+    if (!h) { set_error(e + ": h is 0"); return RT_ERROR_INVALID; }
+    if ((uint64_t)w*h > 0xFFFFFFFFull) { set_error(e + ": w*h must be below 2^32"); return RT_ERROR_INVALID; }
+    if (!s) { set_error(e + ": null scene"); return RT_ERROR_INVALID; }
+    return RT_OK;
+}
+}  // namespace
+
+int rt_gbuffer_device(rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t w, uint32_t h,
+                      rt_gbuffer_texel* d_out, void* hip_stream) {
+    int err = check_gbuffer("rt_gbuffer_device", s, c, w, h, d_out, "d_out");
+    if (err) return err;
+    err = bind_device(s->device);
+    if (err) return err;
+    // the spill area of the largest grid, once per scene (rt_scene_free frees it)
+    if (!s->gbuf_spill)
+        HIP_OK(hipMalloc(&s->gbuf_spill, sizeof(uint2)*(size_t)(STACK_DEPTH - STACK_LDS)*GB_MAX_GRID*GB_BLOCK));
+    GbufParams gp;
+    gp.cp = rv3(c->p); gp.cx = rv3(c->x); gp.cy = rv3(c->y); gp.cz = rv3(c->z);
+    gp.focus_distance = c->focus_distance;
+    gp.film_distance = c->film_distance;
+    gp.half_film_w = c->half_film_w;
+    gp.half_film_h = c->half_film_h;
+    gp.lens_distortion = lens_distortion;
+    gp.w = w; gp.h = h;
+    const uint64_t blocks = ((uint64_t)w*h + GB_BLOCK - 1) / GB_BLOCK;
+    const uint32_t grid = blocks < GB_MAX_GRID ? (uint32_t)blocks : GB_MAX_GRID;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    k_gbuffer<<<grid, GB_BLOCK, 0, stream>>>(s->ds, gp, d_out, s->gbuf_spill);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
+int rt_gbuffer(rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t w, uint32_t h, rt_gbuffer_texel* out) {
+    int err = check_gbuffer("rt_gbuffer", s, c, w, h, out, "out");
+    if (err) return err;
+    err = bind_device(s->device);
+    if (err) return err;
+    const size_t bytes = sizeof(rt_gbuffer_texel)*(size_t)w*h;
+    rt_gbuffer_texel* d_o = nullptr;
+    if (hipMalloc(&d_o, bytes) != hipSuccess) { set_error("rt_gbuffer: hipMalloc"); return RT_ERROR_OUT_OF_MEMORY; }
+    err = rt_gbuffer_device(s, c, lens_distortion, w, h, d_o, nullptr);
+    if (!err && hipMemcpy(out, d_o, bytes, hipMemcpyDeviceToHost) != hipSuccess) { set_error("rt_gbuffer: copy out"); err = RT_ERROR_DEVICE; }
+    (void)hipFree(d_o);
+    return err;
 }
 
 }  // extern "C"

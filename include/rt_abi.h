@@ -746,6 +746,104 @@ int rt_render_picture_robust(rt_scene* scene, const rt_camera* camera, const rt_
                              const rt_denoise_features_params* dp, uint32_t guide_spp, uint32_t* out_bgra,
                              rt_stats* stats);
 
+/* Temporal accumulation (beyond the reference, whose main loop resets its back buffer whenever the camera
+ * moves, RT/raytracer.cpp:711-720; an opt-in: no other entry calls it).  Two device parts and a driver:
+ * a primary-hit G-buffer, a stage that reprojects the previous frame's history through it and blends the
+ * current frame in, and one frame of the loop written on the public entries.  DESIGN.md ("Temporal
+ * accumulation") defines every operation; both kernels match the plain-C restatement
+ * tests/ref_temporal/ref_temporal.c bit for bit.
+ *
+ * The G-buffer: one closest-hit ray per pixel (x, y), render_tile's camera ray (RT/raytracer.cpp:397-460)
+ * without jitter and without the lens offset (a pinhole at camera->p), max_t FLT_MAX, ignored primitive 0.
+ * A hit's texel is what rt_debug_intersect(occlusion = 0) returns for that ray: p = hit_p, t, n, primitive
+ * (with RT_HIT_PLANE_BIT).  A miss is {p = the ray's direction, t = 0, n = 0, primitive = RT_HIT_MISS}: the
+ * sky depends on the direction only, and the stage reprojects it that way. */
+typedef struct rt_gbuffer_texel { rt_v3 p; float t; rt_v3 n; uint32_t primitive; } rt_gbuffer_texel;  /* 32 B */
+/* d_out: w*h texels on the scene's device.  A fixed grid strides over the pixels; its traversal spill area
+ * is allocated with the scene on the first call and freed by rt_scene_free, so later calls allocate nothing.
+ * `hip_stream` may be NULL; returns after the kernel has completed.  RT_ERROR_INVALID by name, before the
+ * device is touched: a NULL scene, camera or output, w or h of 0, w*h of 2^32 or more. */
+int rt_gbuffer_device(rt_scene* scene, const rt_camera* camera, float lens_distortion, uint32_t w, uint32_t h,
+                      rt_gbuffer_texel* d_out, void* hip_stream);
+/* Same, into host memory. */
+int rt_gbuffer(rt_scene* scene, const rt_camera* camera, float lens_distortion, uint32_t w, uint32_t h,
+               rt_gbuffer_texel* out);
+
+/* The accumulate stage, one thread per pixel.  In short:
+ *   - d_current is an accumulation buffer (sum w*rgb, sum w).  The denoise stage's validity rule applies to
+ *     it: weight > 0.001f and a finite resolved colour.  An invalid pixel comes out as it went in (all four
+ *     floats) with length 0, and is never used as a tap by the next frame;
+ *   - the resolved colour c is clamped to [0, firefly_clamp] per channel (no upper clamp when 0);
+ *   - without history (the three d_prev_* pointers NULL: all of them or none) the pixel is {c, 1}, length 1;
+ *   - the point P = texel.p of a hit, prev_camera->p + texel.p of a miss, is projected into the previous
+ *     camera, prev_lens_distortion is undone by a fixed count of clamped Newton steps (a point beyond the
+ *     image's distorted corner radius has no history), and the previous history is read there: the one pixel at the rounded position when both coordinates lie within `snap`
+ *     of an integer (a standing camera does not blur its history), the four bilinear taps otherwise;
+ *   - a tap counts when it lies in the image, its previous length is >= 1, its history is finite, its
+ *     previous texel names the same primitive (as integers) and, for hits, dot(n, n_prev) >= normal_cos and
+ *     |dot(p_prev - P, n)| <= plane_tolerance * t;
+ *   - with W = the valid taps' weight > 0: hist and L their weighted means, N = min(L + 1, max_history),
+ *     out = hist + (c - hist) * (1/N) (c itself when N is 1), length N.  Otherwise {c, 1}, length 1.
+ * d_history is w*h float4 {r, g, b, 1}: rt_denoise*_device and rt_postprocess_device take it as it is.
+ * d_length is one float per pixel. */
+typedef struct rt_temporal_params {
+    float   max_history;      /* >= 1; 1 = no history (output is the clamped current frame) */
+    float   normal_cos;       /* a tap needs dot(n_cur, n_prev) >= this */
+    float   plane_tolerance;  /* and |dot(p_prev - P, n_cur)| <= this * t_cur */
+    float   snap;             /* pixels: within this of an integer position, one tap instead of four */
+    float   firefly_clamp;    /* as rt_denoise_params; 0 = none */
+    int32_t reserved[3];
+} rt_temporal_params;
+int rt_temporal_default_params(rt_temporal_params* out);      /* 32, 0.9, 0.02, 1/32, 10; no device needed */
+/* Device pointers on `device`.  The inputs are only read; d_history and d_length may alias no previous
+ * buffer.  `hip_stream` may be NULL; returns after the kernel has completed.  RT_ERROR_INVALID by name,
+ * before the device is touched: a NULL d_current, d_gbuffer, parameter, d_history or d_length; some but not
+ * all of d_prev_history, d_prev_length and d_prev_gbuffer NULL; a NULL prev_camera with history; w or h of 0;
+ * max_history < 1 or non-finite; a negative or non-finite plane_tolerance, snap or firefly_clamp; normal_cos
+ * outside [-1, 1]; d_history equal to d_prev_history or d_length to d_prev_length. */
+int rt_temporal_accumulate_device(int device, const float* d_current, const rt_gbuffer_texel* d_gbuffer,
+                                  const float* d_prev_history, const float* d_prev_length,
+                                  const rt_gbuffer_texel* d_prev_gbuffer, const rt_camera* prev_camera,
+                                  float prev_lens_distortion, uint32_t w, uint32_t h, const rt_temporal_params* p,
+                                  float* d_history, float* d_length, void* hip_stream);
+/* Same, from and to host memory.  RT_ERROR_NO_DEVICE without a GPU (after the argument checks). */
+int rt_temporal_accumulate(int device, const float* current, const rt_gbuffer_texel* gbuffer,
+                           const float* prev_history, const float* prev_length,
+                           const rt_gbuffer_texel* prev_gbuffer, const rt_camera* prev_camera,
+                           float prev_lens_distortion, uint32_t w, uint32_t h, const rt_temporal_params* p,
+                           float* history, float* length);
+
+/* The driver: one frame of an interactive loop, written on the public entries.  `state` is the caller's; all
+ * zero means no history.  d_workspace (rt_temporal_workspace_bytes(w, h) bytes on the scene's device: the
+ * current frame, then two sets of G-buffer, history and length) is the caller's too and lives as long as the
+ * state.  A frame zeroes the current buffer, renders into it with rt_render_device (the caller's settings
+ * and frame_count), writes set [parity]'s G-buffer with rt_gbuffer_device (settings->lens_distortion), runs
+ * rt_temporal_accumulate_device against set [parity ^ 1] and state->camera (without history when
+ * state->frames is 0 or state->w / state->h differ from w / h: the state restarts), copies the history to
+ * d_out (w*h float4) and the length to d_length_out (w*h floats; may be NULL), then stores the camera and the
+ * lens distortion, flips parity and increments frames.  rt_cancel ends the call with RT_ERROR_CANCELLED and
+ * leaves `state` and the outputs as they were.  `stats` is the beauty frame's.  RT_ERROR_INVALID by name
+ * before the device is touched: a NULL parameter, state, workspace, settings, camera, filter, tiles, output
+ * or scene; w or h of 0; a state's parity above 1; the parameter refusals of the stage. */
+size_t rt_temporal_workspace_bytes(uint32_t w, uint32_t h);   /* current 16 + 2 x (32 + 16 + 4) bytes per pixel; no device needed */
+typedef struct rt_temporal_state {   /* the caller's; all zero = no history */
+    uint32_t  w, h, frames, parity;
+    rt_camera camera;
+    float     lens_distortion;
+    void*     d_workspace;
+} rt_temporal_state;
+int rt_render_temporal_device(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                              const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                              uint32_t w, uint32_t h, uint32_t frame_count, const rt_temporal_params* p,
+                              rt_temporal_state* state, float* d_out, float* d_length_out, void* hip_stream,
+                              rt_stats* stats);
+/* Same, with out_pixels (w*h float4) and out_length (w*h floats; may be NULL) in host memory; the state's
+ * workspace stays on the device. */
+int rt_render_temporal(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                       const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                       uint32_t w, uint32_t h, uint32_t frame_count, const rt_temporal_params* p,
+                       rt_temporal_state* state, float* out_pixels, float* out_length, rt_stats* stats);
+
 /* The reference's top-down BVH builders on the device (RT/bvh.cpp:222-326 with
  * partition_midpoint :53-61, partition_sah_binned :138-213 or the full SAH sweep
  * partition_objects_sah / evaluate_sah :63-131, the partition of :26-51): one launch per
