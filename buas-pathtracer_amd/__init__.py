@@ -23,7 +23,8 @@ import numpy as np
 from . import abi
 from .abi import (V3, v3, M4x4Inv, Material, Camera, Settings, FilterCache, PostSettings, TileSet, Stats,
                   AccumulationBuffer, RayQuery, HitRecord, BvhInfo, DenoiseParams, DenoiseFeaturesParams,
-                  TileErrorParams, AdaptiveParams, RobustParams, GBufferTexel, TemporalParams, TemporalState)
+                  TileErrorParams, AdaptiveParams, RobustParams, GBufferTexel, TemporalParams, TemporalState,
+                  DenoiseVarianceParams, TemporalFilteredState)
 
 __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settings", "load_reconstruction_kernel",
            "translate", "scale", "rotate_x", "rotate_y", "rotate_z", "identity", "aim_camera", "aim_camera_at",
@@ -34,7 +35,11 @@ __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settin
            "denoise_features_workspace_bytes", "TileErrorParams", "AdaptiveParams", "default_tile_error_params",
            "default_adaptive_params", "adaptive_workspace_bytes", "tile_error", "RobustParams", "default_robust_params",
            "robust_workspace_bytes", "robust_combine", "GBufferTexel", "TemporalParams", "TemporalState",
-           "default_temporal_params", "temporal_workspace_bytes", "temporal_accumulate", "temporal_accumulate_device"]
+           "default_temporal_params", "temporal_workspace_bytes", "temporal_accumulate", "temporal_accumulate_device",
+           "DenoiseVarianceParams", "TemporalFilteredState", "default_denoise_variance_params",
+           "denoise_variance_workspace_bytes", "temporal_filtered_workspace_bytes", "temporal_accumulate_moments",
+           "temporal_accumulate_moments_device", "temporal_variance", "temporal_variance_device", "denoise_variance",
+           "denoise_variance_device"]
 
 PI_32 = 3.14159265359
 DEG_TO_RAD = 6.28318530717 / 360.0
@@ -589,6 +594,48 @@ class DeviceScene:
                                                C.c_void_p(stream) if stream else None, C.byref(stats)))
         return stats
 
+    def render_temporal_filtered(self, camera, settings, filter_cache, w, h, state, params=None, filter_params=None,
+                                 spatial_below=abi.RT_TEMPORAL_SPATIAL_BELOW_DEFAULT, frame_count=0, total_frame_index=0,
+                                 tile=64, shard_index=0, shard_count=1, want_extras=True):
+        """rt_render_temporal_filtered: one frame of the loop with the variance-guided filter.  `state` is a
+        TemporalFilteredState whose d_workspace points at temporal_filtered_workspace_bytes(w, h) bytes on the device
+        (all else zero at the start); it is updated in place -> (filtered float32 [h,w,4] = {r, g, b, 1}, then the
+        unfiltered history [h,w,4], its length [h,w] and the variance [h,w], or three None, the beauty frame's stats)."""
+        if params is None:
+            params = default_temporal_params()
+        if filter_params is None:
+            filter_params = default_denoise_variance_params()
+        out = np.zeros((h, w, 4), np.float32)
+        hist = np.zeros((h, w, 4), np.float32) if want_extras else None
+        length = np.zeros((h, w), np.float32) if want_extras else None
+        var = np.zeros((h, w), np.float32) if want_extras else None
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        fp = C.POINTER(C.c_float)
+        opt = lambda a: a.ctypes.data_as(fp) if a is not None else None
+        _check(lib().rt_render_temporal_filtered(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                                 C.byref(tiles), total_frame_index, w, h, frame_count, C.byref(params),
+                                                 float(spatial_below), C.byref(filter_params), C.byref(state),
+                                                 out.ctypes.data_as(fp), opt(hist), opt(length), opt(var), C.byref(stats)))
+        return out, hist, length, var, stats
+
+    def render_temporal_filtered_device(self, camera, settings, filter_cache, w, h, params, filter_params, state, d_out,
+                                        d_history_out=None, d_length_out=None, d_variance_out=None,
+                                        spatial_below=abi.RT_TEMPORAL_SPATIAL_BELOW_DEFAULT, stream=None, frame_count=0,
+                                        total_frame_index=0, tile=64, shard_index=0, shard_count=1):
+        """rt_render_temporal_filtered_device into device pointers (d_out w*h float4; the unfiltered history w*h float4,
+        its length and the variance w*h floats each, or None); `state` as for render_temporal_filtered -> the beauty
+        frame's stats."""
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        vp = lambda a: C.c_void_p(a) if a else None
+        _check(lib().rt_render_temporal_filtered_device(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                                        C.byref(tiles), total_frame_index, w, h, frame_count,
+                                                        C.byref(params), float(spatial_below), C.byref(filter_params),
+                                                        C.byref(state), vp(d_out), vp(d_history_out), vp(d_length_out),
+                                                        vp(d_variance_out), vp(stream), C.byref(stats)))
+        return stats
+
     def configure(self, **fields):
         """rt_scene_set_config with the named fields changed, e.g. configure(partitions=1,
         splat_mode=abi.RT_SPLAT_EXACT).  Returns the previous configuration (pass it to
@@ -833,6 +880,122 @@ def temporal_accumulate_device(d_current, d_gbuffer, d_prev_history, d_prev_leng
                                                vp(d_prev_gbuffer), None if prev_camera is None else C.byref(prev_camera),
                                                float(prev_lens_distortion), w, h, C.byref(params), vp(d_history),
                                                vp(d_length), vp(stream)))
+
+
+def default_denoise_variance_params():
+    """rt_denoise_variance_default_params (no device needed) -> DenoiseVarianceParams."""
+    p = DenoiseVarianceParams()
+    _check(lib().rt_denoise_variance_default_params(C.byref(p)))
+    return p
+
+
+def denoise_variance_workspace_bytes(w, h):
+    """rt_denoise_variance_workspace_bytes (no device needed): the filter's workspace, 40 bytes per pixel."""
+    return int(lib().rt_denoise_variance_workspace_bytes(w, h))
+
+
+def temporal_filtered_workspace_bytes(w, h):
+    """rt_temporal_filtered_workspace_bytes (no device needed): the filtered driver's workspace, 180 bytes per pixel."""
+    return int(lib().rt_temporal_filtered_workspace_bytes(w, h))
+
+
+def temporal_accumulate_moments(current, gbuffer, prev=None, prev_camera=None, prev_lens_distortion=0.0, params=None,
+                                device=0):
+    """The accumulate stage with moments on the GPU (rt_temporal_accumulate_moments): temporal_accumulate's arguments with
+    prev = (history (h, w, 4), length (h, w), gbuffer (h, w), moments (h, w, 2)) -> (history, length, moments (h, w, 2))."""
+    current = np.ascontiguousarray(current, np.float32)
+    h, w, _ = current.shape
+    gbuffer = np.ascontiguousarray(gbuffer, abi.GBUFFER_DTYPE)
+    assert gbuffer.shape == (h, w)
+    if params is None:
+        params = default_temporal_params()
+    fp, gp = C.POINTER(C.c_float), C.POINTER(GBufferTexel)
+    ph = pl = pg = pm = None
+    if prev is not None:
+        ph = np.ascontiguousarray(prev[0], np.float32)
+        pl = np.ascontiguousarray(prev[1], np.float32)
+        pg = np.ascontiguousarray(prev[2], abi.GBUFFER_DTYPE)
+        pm = np.ascontiguousarray(prev[3], np.float32)
+        assert ph.shape == (h, w, 4) and pl.shape == (h, w) and pg.shape == (h, w) and pm.shape == (h, w, 2)
+    history = np.zeros((h, w, 4), np.float32)
+    length = np.zeros((h, w), np.float32)
+    moments = np.zeros((h, w, 2), np.float32)
+    _check(lib().rt_temporal_accumulate_moments(device, current.ctypes.data_as(fp), gbuffer.ctypes.data_as(gp),
+                                                None if ph is None else ph.ctypes.data_as(fp),
+                                                None if pl is None else pl.ctypes.data_as(fp),
+                                                None if pg is None else pg.ctypes.data_as(gp),
+                                                None if pm is None else pm.ctypes.data_as(fp),
+                                                None if prev_camera is None else C.byref(prev_camera),
+                                                float(prev_lens_distortion), w, h, C.byref(params),
+                                                history.ctypes.data_as(fp), length.ctypes.data_as(fp),
+                                                moments.ctypes.data_as(fp)))
+    return history, length, moments
+
+
+def temporal_accumulate_moments_device(d_current, d_gbuffer, d_prev_history, d_prev_length, d_prev_gbuffer, d_prev_moments,
+                                       prev_camera, prev_lens_distortion, w, h, params, d_history, d_length, d_moments,
+                                       device=0, stream=None):
+    """rt_temporal_accumulate_moments_device on device pointers (the four d_prev_* all None for no history)."""
+    vp = lambda a: C.c_void_p(a) if a else None
+    _check(lib().rt_temporal_accumulate_moments_device(device, vp(d_current), vp(d_gbuffer), vp(d_prev_history),
+                                                       vp(d_prev_length), vp(d_prev_gbuffer), vp(d_prev_moments),
+                                                       None if prev_camera is None else C.byref(prev_camera),
+                                                       float(prev_lens_distortion), w, h, C.byref(params), vp(d_history),
+                                                       vp(d_length), vp(d_moments), vp(stream)))
+
+
+def temporal_variance(moments, length, gbuffer, params=None, spatial_below=abi.RT_TEMPORAL_SPATIAL_BELOW_DEFAULT, device=0):
+    """The variance of the history on the GPU (rt_temporal_variance): moments (h, w, 2), length (h, w) and the frame's
+    G-buffer (h, w) -> variance (h, w)."""
+    moments = np.ascontiguousarray(moments, np.float32)
+    h, w, _ = moments.shape
+    length = np.ascontiguousarray(length, np.float32)
+    gbuffer = np.ascontiguousarray(gbuffer, abi.GBUFFER_DTYPE)
+    assert length.shape == (h, w) and gbuffer.shape == (h, w)
+    if params is None:
+        params = default_temporal_params()
+    fp = C.POINTER(C.c_float)
+    out = np.zeros((h, w), np.float32)
+    _check(lib().rt_temporal_variance(device, moments.ctypes.data_as(fp), length.ctypes.data_as(fp),
+                                      gbuffer.ctypes.data_as(C.POINTER(GBufferTexel)), w, h, C.byref(params),
+                                      float(spatial_below), out.ctypes.data_as(fp)))
+    return out
+
+
+def temporal_variance_device(d_moments, d_length, d_gbuffer, w, h, params, spatial_below, d_variance, device=0, stream=None):
+    """rt_temporal_variance_device on device pointers."""
+    vp = lambda a: C.c_void_p(a) if a else None
+    _check(lib().rt_temporal_variance_device(device, vp(d_moments), vp(d_length), vp(d_gbuffer), w, h, C.byref(params),
+                                             float(spatial_below), vp(d_variance), vp(stream)))
+
+
+def denoise_variance(color, variance, gbuffer, params=None, device=0, want_variance=True):
+    """The variance-guided filter on the GPU (rt_denoise_variance): a host colour buffer (h, w, 4) (a history {r, g, b, 1}
+    or an accumulation buffer), its variance (h, w) and the frame's G-buffer (h, w) -> (out (h, w, 4), the filtered
+    variance (h, w) or None)."""
+    color = np.ascontiguousarray(color, np.float32)
+    h, w, _ = color.shape
+    variance = np.ascontiguousarray(variance, np.float32)
+    gbuffer = np.ascontiguousarray(gbuffer, abi.GBUFFER_DTYPE)
+    assert variance.shape == (h, w) and gbuffer.shape == (h, w)
+    if params is None:
+        params = default_denoise_variance_params()
+    fp = C.POINTER(C.c_float)
+    out = np.zeros((h, w, 4), np.float32)
+    var_out = np.zeros((h, w), np.float32) if want_variance else None
+    _check(lib().rt_denoise_variance(device, color.ctypes.data_as(fp), variance.ctypes.data_as(fp),
+                                     gbuffer.ctypes.data_as(C.POINTER(GBufferTexel)), w, h, C.byref(params),
+                                     out.ctypes.data_as(fp), var_out.ctypes.data_as(fp) if want_variance else None))
+    return out, var_out
+
+
+def denoise_variance_device(d_color, d_variance, d_gbuffer, w, h, params, d_out, d_variance_out=None, d_workspace=None,
+                            device=0, stream=None):
+    """rt_denoise_variance_device on device pointers (d_out may be d_color, d_variance_out may be d_variance or None;
+    d_workspace None: the call allocates its own)."""
+    vp = lambda a: C.c_void_p(a) if a else None
+    _check(lib().rt_denoise_variance_device(device, vp(d_color), vp(d_variance), vp(d_gbuffer), w, h, C.byref(params),
+                                            vp(d_workspace), vp(d_out), vp(d_variance_out), vp(stream)))
 
 
 def write_bitmap(path, bgra):

@@ -232,6 +232,20 @@ class TemporalState(C.Structure):      # rt_temporal_state (temporal accumulatio
                 ("camera", Camera), ("lens_distortion", C.c_float), ("d_workspace", C.c_void_p)]
 
 
+class DenoiseVarianceParams(C.Structure):   # rt_denoise_variance_params (variance-guided filtering: the filter), 32 bytes
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_plane", C.c_float), ("variance_epsilon", C.c_float), ("firefly_clamp", C.c_float),
+                ("reserved", C.c_int32 * 2)]
+
+
+class TemporalFilteredState(C.Structure):   # rt_temporal_filtered_state (variance-guided filtering: the driver's)
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("frames", C.c_uint32), ("parity", C.c_uint32),
+                ("camera", Camera), ("lens_distortion", C.c_float), ("d_workspace", C.c_void_p)]
+
+
+RT_TEMPORAL_SPATIAL_BELOW_DEFAULT = 4.0
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("node_count", C.c_uint32), ("leaf_count", C.c_uint32), ("max_depth", C.c_uint32),
                 ("max_leaf_size", C.c_uint32)]
@@ -364,6 +378,31 @@ ABI_FUNCTIONS = {
     "rt_render_temporal": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
                                      C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams), P(TemporalState),
                                      P(C.c_float), P(C.c_float), P(Stats)]),
+    "rt_temporal_accumulate_moments_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, P(Camera), C.c_float, C.c_uint32, C.c_uint32,
+                                                        P(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_temporal_accumulate_moments": (C.c_int, [C.c_int, P(C.c_float), P(GBufferTexel), P(C.c_float), P(C.c_float),
+                                                 P(GBufferTexel), P(C.c_float), P(Camera), C.c_float, C.c_uint32, C.c_uint32,
+                                                 P(TemporalParams), P(C.c_float), P(C.c_float), P(C.c_float)]),
+    "rt_temporal_variance_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                              P(TemporalParams), C.c_float, C.c_void_p, C.c_void_p]),
+    "rt_temporal_variance": (C.c_int, [C.c_int, P(C.c_float), P(C.c_float), P(GBufferTexel), C.c_uint32, C.c_uint32,
+                                       P(TemporalParams), C.c_float, P(C.c_float)]),
+    "rt_denoise_variance_default_params": (C.c_int, [P(DenoiseVarianceParams)]),
+    "rt_denoise_variance_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rt_denoise_variance_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                             P(DenoiseVarianceParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise_variance": (C.c_int, [C.c_int, P(C.c_float), P(C.c_float), P(GBufferTexel), C.c_uint32, C.c_uint32,
+                                      P(DenoiseVarianceParams), P(C.c_float), P(C.c_float)]),
+    "rt_temporal_filtered_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rt_render_temporal_filtered_device": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet),
+                                                     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams),
+                                                     C.c_float, P(DenoiseVarianceParams), P(TemporalFilteredState),
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(Stats)]),
+    "rt_render_temporal_filtered": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
+                                              C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams), C.c_float,
+                                              P(DenoiseVarianceParams), P(TemporalFilteredState), P(C.c_float),
+                                              P(C.c_float), P(C.c_float), P(C.c_float), P(Stats)]),
 }
 
 HOST_FUNCTIONS = {

@@ -844,6 +844,128 @@ int rt_render_temporal(rt_scene* scene, const rt_camera* camera, const rt_settin
                        uint32_t w, uint32_t h, uint32_t frame_count, const rt_temporal_params* p,
                        rt_temporal_state* state, float* out_pixels, float* out_length, rt_stats* stats);
 
+/* Variance-guided filtering of the temporal history (beyond the reference; after Schied et al., "Spatiotemporal
+ * Variance-Guided Filtering", HPG 2017, in this project's terms; an opt-in: no other entry calls it, and
+ * rt_render_temporal_device is not touched).  Three device parts and a driver: the accumulate stage with the
+ * first two moments of the tonemapped luminance beside it, the variance of the history from those moments, an
+ * a-trous filter whose colour term is scaled by that variance and whose edge-stopping terms come from the
+ * G-buffer (no guide frames), and one frame of the loop written on the public entries.  DESIGN.md
+ * ("Variance-guided filtering") defines every operation; the kernels match the plain-C restatement
+ * tests/ref_svgf/ref_svgf.c bit for bit.  Throughout, lum(c) = (0.2126 r + 0.7152 g) + 0.0722 b and
+ * tm(c) = 1 - expf(-lum(c)), the denoise stage's l, in [0, 1].
+ *
+ * Accumulate with moments: rt_temporal_accumulate_device's arguments and operations, and d_history and d_length
+ * equal to its outputs bit for bit; in addition d_prev_moments (all-or-none with the other three previous
+ * buffers) and d_moments, two floats {m1, m2} per pixel (it may not alias d_prev_moments).  An invalid pixel
+ * writes {0, 0}.  With t = tm(c) of the clamped current colour: each valid tap also adds wt * m_prev to S1 and S2
+ * (the moments take no part in a tap's validity); with W > 0, h = S / W and m = h + ({t, t*t} - h) * (1/N)
+ * ({t, t*t} itself when N is 1); without a valid tap or without history {t, t*t}.  The refusals are the
+ * accumulate stage's, by name, and a NULL d_moments, a NULL d_prev_moments beside other previous buffers (or
+ * the reverse) and d_moments equal to d_prev_moments. */
+int rt_temporal_accumulate_moments_device(int device, const float* d_current, const rt_gbuffer_texel* d_gbuffer,
+                                          const float* d_prev_history, const float* d_prev_length,
+                                          const rt_gbuffer_texel* d_prev_gbuffer, const float* d_prev_moments,
+                                          const rt_camera* prev_camera, float prev_lens_distortion, uint32_t w,
+                                          uint32_t h, const rt_temporal_params* p, float* d_history, float* d_length,
+                                          float* d_moments, void* hip_stream);
+/* Same, from and to host memory.  RT_ERROR_NO_DEVICE without a GPU (after the argument checks). */
+int rt_temporal_accumulate_moments(int device, const float* current, const rt_gbuffer_texel* gbuffer,
+                                   const float* prev_history, const float* prev_length,
+                                   const rt_gbuffer_texel* prev_gbuffer, const float* prev_moments,
+                                   const rt_camera* prev_camera, float prev_lens_distortion, uint32_t w, uint32_t h,
+                                   const rt_temporal_params* p, float* history, float* length, float* moments);
+
+/* The variance of the history, one float per pixel: the variance of the mean that the history holds, so a long
+ * history filters less.  A pixel whose length is not >= 1 gets 0.  With length >= spatial_below,
+ * s2 = max(m2 - m1*m1, 0).  Otherwise the moments are averaged over a 7x7 window of the current frame: a
+ * neighbour counts when it lies in the image, its length is >= 1 and it is the same surface by the accumulate
+ * stage's rule within this frame's G-buffer (the same primitive and, for hits, dot(n_p, n_q) >= p->normal_cos
+ * and |dot(p_q - p_p, n_p)| <= p->plane_tolerance * t_p); the centre always counts; s2 from the window's means.
+ * The output is s2 / length.  Of `p` only normal_cos and plane_tolerance are used, and all of it is checked.
+ * RT_ERROR_INVALID by name before the device is touched: a NULL pointer, w or h of 0, the parameter refusals
+ * of the accumulate stage, a negative or non-finite spatial_below, d_variance equal to an input. */
+#define RT_TEMPORAL_SPATIAL_BELOW_DEFAULT 4.0f
+int rt_temporal_variance_device(int device, const float* d_moments, const float* d_length,
+                                const rt_gbuffer_texel* d_gbuffer, uint32_t w, uint32_t h, const rt_temporal_params* p,
+                                float spatial_below, float* d_variance, void* hip_stream);
+/* Same, from and to host memory.  RT_ERROR_NO_DEVICE without a GPU (after the argument checks). */
+int rt_temporal_variance(int device, const float* moments, const float* length, const rt_gbuffer_texel* gbuffer,
+                         uint32_t w, uint32_t h, const rt_temporal_params* p, float spatial_below, float* variance);
+
+/* The variance-guided filter.  d_color is w*h float4, resolved and clamped as the denoise stage resolves beauty
+ * (a history {r, g, b, 1} passes as it is); d_variance one float per pixel; d_gbuffer the frame's texels.  A
+ * pixel is valid by the denoise stage's rule on the colour and when its variance is >= 0 and finite; invalid
+ * pixels come out as they went in (all four floats, and their variance) and contribute to no neighbour.
+ * Iteration i (step 2^i) of `iterations`, for a valid pixel p: gv = the 3x3 Gaussian {1/16, 1/8, 1/4} of the
+ * current variance over the valid neighbours at distance 1; the 5x5 B3-spline kernel with holes of the denoise
+ * stage, skipping taps outside the image, invalid taps and taps where exactly one of p and q is a miss; each
+ * tap weighted by expf(-e), e = |l(p) - l(q)| / (sigma_color sqrt(gv) + variance_epsilon)
+ * + |n_p - n_q|^2 / sigma_normal^2 + (dot(p_q - p_p, n_p) / t_p)^2 / sigma_plane^2 (the last two for a hit p
+ * only; l = tm of the current colour); c' = sum(wt c) / sum(wt), var' = sum(wt^2 var) / sum(wt)^2.  A valid pixel
+ * comes out as {r, g, b, 1.0f}, so rt_postprocess_device takes the buffer as it is. */
+typedef struct rt_denoise_variance_params {
+    int32_t iterations;        /* 1..8 */
+    float   sigma_color;       /* in standard deviations of the tonemapped luminance; 0 = term off */
+    float   sigma_normal;      /* on the raw normals' difference; 0 = term off */
+    float   sigma_plane;       /* on the offset along p's normal over p's distance; 0 = term off */
+    float   variance_epsilon;  /* > 0: the colour term's floor where the variance is 0 */
+    float   firefly_clamp;     /* as rt_denoise_params; 0 = none */
+    int32_t reserved[2];
+} rt_denoise_variance_params;
+int    rt_denoise_variance_default_params(rt_denoise_variance_params* out);   /* 4, 4, 0.2, 0.02, 0.03, 10; no device needed */
+size_t rt_denoise_variance_workspace_bytes(uint32_t w, uint32_t h);           /* 40 bytes per pixel; no device needed */
+/* Device pointers on `device`; d_out (w*h float4) may equal d_color, d_variance_out (w*h floats; may be NULL)
+ * may equal d_variance.  d_workspace holds rt_denoise_variance_workspace_bytes(w, h) bytes; with NULL the call
+ * allocates and frees its own.  `hip_stream` may be NULL; returns after the filter has completed.
+ * RT_ERROR_INVALID by name before the device is touched: a NULL d_color, d_variance, d_gbuffer, parameter or
+ * d_out; w or h of 0; iterations outside 1..8; a negative or non-finite sigma or clamp; a variance_epsilon that
+ * is not finite and > 0; d_out equal to d_variance or d_gbuffer; d_variance_out equal to d_color, d_gbuffer or
+ * d_out; w or h above 65535; a d_gbuffer or d_workspace that is not 16-byte aligned. */
+int rt_denoise_variance_device(int device, const float* d_color, const float* d_variance,
+                               const rt_gbuffer_texel* d_gbuffer, uint32_t w, uint32_t h,
+                               const rt_denoise_variance_params* p, void* d_workspace, float* d_out,
+                               float* d_variance_out, void* hip_stream);
+/* Same, from and to host memory.  RT_ERROR_NO_DEVICE without a GPU (after the argument checks). */
+int rt_denoise_variance(int device, const float* color, const float* variance, const rt_gbuffer_texel* gbuffer,
+                        uint32_t w, uint32_t h, const rt_denoise_variance_params* p, float* out, float* variance_out);
+
+/* The driver: one frame of the interactive loop with the filter, written on the public entries.  `state` is the
+ * caller's, all zero means no history; d_workspace (rt_temporal_filtered_workspace_bytes(w, h) bytes on the
+ * scene's device, 16-byte aligned) is the caller's too and lives as long as the state.  A frame zeroes the
+ * current buffer, renders into it with rt_render_device, writes set [parity]'s G-buffer with rt_gbuffer_device,
+ * runs rt_temporal_accumulate_moments_device against set [parity ^ 1] and state->camera (without history when
+ * state->frames is 0 or the frame size changed: the state restarts), rt_temporal_variance_device on the new
+ * set, and rt_denoise_variance_device from the new history into d_out (w*h float4).  The history that the
+ * next frame reads stays the unfiltered one.  The optional outputs (each may be NULL) are that unfiltered
+ * history (w*h float4), its length and the variance the filter was given (w*h floats each).  Then the camera
+ * and the lens distortion are stored, parity flips and frames increments.  rt_cancel ends the call with
+ * RT_ERROR_CANCELLED and leaves `state` and the outputs as they were.  `stats` is the beauty frame's.
+ * RT_ERROR_INVALID by name before the device is touched, in rt_render_temporal_device's order: the parameter
+ * refusals of the three stages, then a NULL state, workspace, settings, camera, filter, tiles, output or scene,
+ * w or h of 0, a parity above 1. */
+size_t rt_temporal_filtered_workspace_bytes(uint32_t w, uint32_t h);   /* 180 bytes per pixel; no device needed */
+typedef struct rt_temporal_filtered_state {   /* the caller's; all zero = no history */
+    uint32_t  w, h, frames, parity;
+    rt_camera camera;
+    float     lens_distortion;
+    void*     d_workspace;
+} rt_temporal_filtered_state;
+int rt_render_temporal_filtered_device(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                                       const rt_filter_cache* filter, const rt_tile_set* tiles,
+                                       uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
+                                       const rt_temporal_params* p, float spatial_below,
+                                       const rt_denoise_variance_params* fp, rt_temporal_filtered_state* state,
+                                       float* d_out, float* d_history_out, float* d_length_out, float* d_variance_out,
+                                       void* hip_stream, rt_stats* stats);
+/* Same, with the four outputs in host memory (all but out_pixels may be NULL); the state's workspace stays on the
+ * device. */
+int rt_render_temporal_filtered(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                                const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                                uint32_t w, uint32_t h, uint32_t frame_count, const rt_temporal_params* p,
+                                float spatial_below, const rt_denoise_variance_params* fp,
+                                rt_temporal_filtered_state* state, float* out_pixels, float* out_history,
+                                float* out_length, float* out_variance, rt_stats* stats);
+
 /* The reference's top-down BVH builders on the device (RT/bvh.cpp:222-326 with
  * partition_midpoint :53-61, partition_sah_binned :138-213 or the full SAH sweep
  * partition_objects_sah / evaluate_sah :63-131, the partition of :26-51): one launch per
