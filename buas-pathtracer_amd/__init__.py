@@ -24,7 +24,7 @@ from . import abi
 from .abi import (V3, v3, M4x4Inv, Material, Camera, Settings, FilterCache, PostSettings, TileSet, Stats,
                   AccumulationBuffer, RayQuery, HitRecord, BvhInfo, DenoiseParams, DenoiseFeaturesParams,
                   TileErrorParams, AdaptiveParams, RobustParams, GBufferTexel, TemporalParams, TemporalState,
-                  DenoiseVarianceParams, TemporalFilteredState)
+                  DenoiseVarianceParams, TemporalFilteredState, MotionEntry, TemporalMotionState)
 
 __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settings", "load_reconstruction_kernel",
            "translate", "scale", "rotate_x", "rotate_y", "rotate_z", "identity", "aim_camera", "aim_camera_at",
@@ -39,7 +39,8 @@ __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settin
            "DenoiseVarianceParams", "TemporalFilteredState", "default_denoise_variance_params",
            "denoise_variance_workspace_bytes", "temporal_filtered_workspace_bytes", "temporal_accumulate_moments",
            "temporal_accumulate_moments_device", "temporal_variance", "temporal_variance_device", "denoise_variance",
-           "denoise_variance_device"]
+           "denoise_variance_device", "MotionEntry", "TemporalMotionState", "motion_table", "temporal_accumulate_motion",
+           "temporal_accumulate_motion_device", "temporal_motion_workspace_bytes"]
 
 PI_32 = 3.14159265359
 DEG_TO_RAD = 6.28318530717 / 360.0
@@ -219,6 +220,12 @@ class Scene:
         if not lib().rth_create_scene_bvh(self._h):
             raise RuntimeError(f"rth_create_scene_bvh failed: {(lib().rth_last_error() or b'').decode()}")
 
+    def set_primitive_transform(self, primitive_id, transform):
+        """rth_set_primitive_transform: move a sphere, box or mesh instance.  Call create_scene_bvh() again before
+        desc() is uploaded or passed to DeviceScene.update_instances."""
+        if not lib().rth_set_primitive_transform(self._h, primitive_id, C.byref(transform)):
+            raise ValueError((lib().rth_last_error() or b"").decode())
+
     def bvh_info(self, mesh_id=None):
         info = BvhInfo()
         if mesh_id is None:
@@ -268,6 +275,24 @@ class DeviceScene:
             self._h = C.c_void_p()
 
     __del__ = close
+
+    def update_instances(self, desc=None):
+        """rt_scene_update_instances: replace the transform-dependent tables (transforms, transform indices, the
+        top-level BVH) with those of `desc` (default: the host scene's desc() as it is now).  No mesh, material or
+        sky array of `desc` is read.  Synchronises the device."""
+        if desc is None:
+            desc = self.scene.desc()
+        _check(lib().rt_scene_update_instances(self._h, C.byref(desc)))
+
+    def primitive_transforms(self):
+        """rt_scene_primitive_transforms: the resolved transform of every primitive as of the upload or the last
+        update -> a structured array (primitive_count,) of abi.M4X4INV_DTYPE."""
+        count = C.c_uint32()
+        _check(lib().rt_scene_primitive_transforms(self._h, 0, None, C.byref(count)))
+        out = np.zeros(count.value, abi.M4X4INV_DTYPE)
+        _check(lib().rt_scene_primitive_transforms(self._h, count.value, out.ctypes.data_as(C.POINTER(M4x4Inv)),
+                                                   C.byref(count)))
+        return out
 
     def render(self, camera, settings, filter_cache, w, h, accum=None, frame_count=0, total_frame_index=0,
                tile=64, shard_index=0, shard_count=1):
@@ -594,6 +619,39 @@ class DeviceScene:
                                                C.c_void_p(stream) if stream else None, C.byref(stats)))
         return stats
 
+    def render_temporal_motion(self, camera, settings, filter_cache, w, h, state, params=None, frame_count=0,
+                               total_frame_index=0, tile=64, shard_index=0, shard_count=1, want_length=True):
+        """rt_render_temporal_motion: render_temporal with a history that follows update_instances.  `state` is a
+        TemporalMotionState whose d_workspace points at temporal_motion_workspace_bytes(w, h, primitive count) bytes
+        on the device and whose transforms / transform_cap name a host array of M4x4Inv (all else zero at the start)
+        -> (history float32 [h,w,4], length float32 [h,w] or None, the beauty frame's stats)."""
+        if params is None:
+            params = default_temporal_params()
+        out = np.zeros((h, w, 4), np.float32)
+        length = np.zeros((h, w), np.float32) if want_length else None
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        fp = C.POINTER(C.c_float)
+        _check(lib().rt_render_temporal_motion(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                               C.byref(tiles), total_frame_index, w, h, frame_count, C.byref(params),
+                                               C.byref(state), out.ctypes.data_as(fp),
+                                               length.ctypes.data_as(fp) if want_length else None, C.byref(stats)))
+        return out, length, stats
+
+    def render_temporal_motion_device(self, camera, settings, filter_cache, w, h, params, state, d_out, d_length_out=None,
+                                      stream=None, frame_count=0, total_frame_index=0, tile=64, shard_index=0,
+                                      shard_count=1):
+        """rt_render_temporal_motion_device into device pointers (as render_temporal_device); `state` as for
+        render_temporal_motion -> the beauty frame's stats."""
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        _check(lib().rt_render_temporal_motion_device(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                                      C.byref(tiles), total_frame_index, w, h, frame_count,
+                                                      C.byref(params), C.byref(state), C.c_void_p(d_out),
+                                                      C.c_void_p(d_length_out) if d_length_out else None,
+                                                      C.c_void_p(stream) if stream else None, C.byref(stats)))
+        return stats
+
     def render_temporal_filtered(self, camera, settings, filter_cache, w, h, state, params=None, filter_params=None,
                                  spatial_below=abi.RT_TEMPORAL_SPATIAL_BELOW_DEFAULT, frame_count=0, total_frame_index=0,
                                  tile=64, shard_index=0, shard_count=1, want_extras=True):
@@ -880,6 +938,78 @@ def temporal_accumulate_device(d_current, d_gbuffer, d_prev_history, d_prev_leng
                                                vp(d_prev_gbuffer), None if prev_camera is None else C.byref(prev_camera),
                                                float(prev_lens_distortion), w, h, C.byref(params), vp(d_history),
                                                vp(d_length), vp(stream)))
+
+
+def temporal_motion_workspace_bytes(w, h, primitive_count):
+    """rt_temporal_motion_workspace_bytes (no device needed): temporal_workspace_bytes and the motion table."""
+    return int(lib().rt_temporal_motion_workspace_bytes(w, h, primitive_count))
+
+
+def motion_table(cur, prev):
+    """rt_motion_table (no device needed): two arrays of abi.M4X4INV_DTYPE (the current and the previous resolved
+    transforms, as DeviceScene.primitive_transforms returns them) -> a structured array of abi.MOTION_DTYPE."""
+    cur = np.ascontiguousarray(cur, abi.M4X4INV_DTYPE)
+    prev = np.ascontiguousarray(prev, abi.M4X4INV_DTYPE)
+    assert cur.shape == prev.shape and cur.ndim == 1
+    out = np.zeros(cur.shape[0], abi.MOTION_DTYPE)
+    mp = C.POINTER(M4x4Inv)
+    _check(lib().rt_motion_table(cur.shape[0], cur.ctypes.data_as(mp), prev.ctypes.data_as(mp),
+                                 out.ctypes.data_as(C.POINTER(MotionEntry))))
+    return out
+
+
+def temporal_accumulate_motion(current, gbuffer, prev=None, prev_camera=None, prev_lens_distortion=0.0, params=None,
+                               motion=None, want_moments=False, want_velocity=False, device=0):
+    """The motion-aware accumulate stage on the GPU (rt_temporal_accumulate_motion): temporal_accumulate's arguments,
+    `motion` a table of abi.MOTION_DTYPE or None, prev = (history, length, gbuffer) and with want_moments also the
+    previous moments (h, w, 2) -> (history, length, moments (h, w, 2) or None, velocity (h, w, 2) or None)."""
+    current = np.ascontiguousarray(current, np.float32)
+    h, w, _ = current.shape
+    gbuffer = np.ascontiguousarray(gbuffer, abi.GBUFFER_DTYPE)
+    assert gbuffer.shape == (h, w)
+    if params is None:
+        params = default_temporal_params()
+    fp, gp = C.POINTER(C.c_float), C.POINTER(GBufferTexel)
+    ph = pl = pg = pm = None
+    if prev is not None:
+        ph = np.ascontiguousarray(prev[0], np.float32)
+        pl = np.ascontiguousarray(prev[1], np.float32)
+        pg = np.ascontiguousarray(prev[2], abi.GBUFFER_DTYPE)
+        assert ph.shape == (h, w, 4) and pl.shape == (h, w) and pg.shape == (h, w)
+        if want_moments:
+            pm = np.ascontiguousarray(prev[3], np.float32)
+            assert pm.shape == (h, w, 2)
+    count = 0
+    if motion is not None:
+        motion = np.ascontiguousarray(motion, abi.MOTION_DTYPE)
+        count = motion.shape[0]
+    history = np.zeros((h, w, 4), np.float32)
+    length = np.zeros((h, w), np.float32)
+    moments = np.zeros((h, w, 2), np.float32) if want_moments else None
+    velocity = np.zeros((h, w, 2), np.float32) if want_velocity else None
+    opt = lambda a, t: None if a is None else a.ctypes.data_as(t)
+    _check(lib().rt_temporal_accumulate_motion(device, current.ctypes.data_as(fp), gbuffer.ctypes.data_as(gp), opt(ph, fp),
+                                               opt(pl, fp), opt(pg, gp),
+                                               None if prev_camera is None else C.byref(prev_camera),
+                                               float(prev_lens_distortion), w, h, C.byref(params),
+                                               history.ctypes.data_as(fp), length.ctypes.data_as(fp),
+                                               opt(motion if count else None, C.POINTER(MotionEntry)), count, opt(pm, fp),
+                                               opt(moments, fp), opt(velocity, fp)))
+    return history, length, moments, velocity
+
+
+def temporal_accumulate_motion_device(d_current, d_gbuffer, d_prev_history, d_prev_length, d_prev_gbuffer, prev_camera,
+                                      prev_lens_distortion, w, h, params, d_history, d_length, d_motion=None, motion_count=0,
+                                      d_prev_moments=None, d_moments=None, d_velocity=None, device=0, stream=None):
+    """rt_temporal_accumulate_motion_device on device pointers (the d_prev_* all None for no history; d_motion,
+    d_moments with d_prev_moments, and d_velocity optional)."""
+    vp = lambda a: C.c_void_p(a) if a else None
+    _check(lib().rt_temporal_accumulate_motion_device(device, vp(d_current), vp(d_gbuffer), vp(d_prev_history),
+                                                      vp(d_prev_length), vp(d_prev_gbuffer),
+                                                      None if prev_camera is None else C.byref(prev_camera),
+                                                      float(prev_lens_distortion), w, h, C.byref(params), vp(d_history),
+                                                      vp(d_length), vp(stream), vp(d_motion), motion_count,
+                                                      vp(d_prev_moments), vp(d_moments), vp(d_velocity)))
 
 
 def default_denoise_variance_params():

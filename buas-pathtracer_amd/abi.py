@@ -246,6 +246,23 @@ class TemporalFilteredState(C.Structure):   # rt_temporal_filtered_state (varian
 RT_TEMPORAL_SPATIAL_BELOW_DEFAULT = 4.0
 
 
+class MotionEntry(C.Structure):        # rt_motion_entry (moving instances: one primitive's rigid motion), 112 bytes
+    _fields_ = [("inv_cur", (C.c_float * 4) * 3), ("fwd_prev", (C.c_float * 4) * 3), ("moved", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+# the numpy layout of a motion table: np.zeros(count, MOTION_DTYPE)
+MOTION_DTYPE = [("inv_cur", "<f4", (3, 4)), ("fwd_prev", "<f4", (3, 4)), ("moved", "<u4"), ("reserved", "<u4", (3,))]
+# and of rt_m4x4inv arrays: np.zeros(count, M4X4INV_DTYPE)
+M4X4INV_DTYPE = [("forward", "<f4", (4, 4)), ("inverse", "<f4", (4, 4))]
+
+
+class TemporalMotionState(C.Structure):     # rt_temporal_motion_state (moving instances: the driver's)
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("frames", C.c_uint32), ("parity", C.c_uint32),
+                ("camera", Camera), ("lens_distortion", C.c_float), ("primitive_count", C.c_uint32),
+                ("transform_cap", C.c_uint32), ("d_workspace", C.c_void_p), ("transforms", C.POINTER(M4x4Inv))]
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("node_count", C.c_uint32), ("leaf_count", C.c_uint32), ("max_depth", C.c_uint32),
                 ("max_leaf_size", C.c_uint32)]
@@ -403,6 +420,24 @@ ABI_FUNCTIONS = {
                                               C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams), C.c_float,
                                               P(DenoiseVarianceParams), P(TemporalFilteredState), P(C.c_float),
                                               P(C.c_float), P(C.c_float), P(C.c_float), P(Stats)]),
+    "rt_scene_update_instances": (C.c_int, [C.c_void_p, P(SceneDesc)]),
+    "rt_scene_primitive_transforms": (C.c_int, [C.c_void_p, C.c_uint32, P(M4x4Inv), P(C.c_uint32)]),
+    "rt_motion_table": (C.c_int, [C.c_uint32, P(M4x4Inv), P(M4x4Inv), P(MotionEntry)]),
+    "rt_temporal_accumulate_motion_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       P(Camera), C.c_float, C.c_uint32, C.c_uint32, P(TemporalParams),
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_temporal_accumulate_motion": (C.c_int, [C.c_int, P(C.c_float), P(GBufferTexel), P(C.c_float), P(C.c_float),
+                                                P(GBufferTexel), P(Camera), C.c_float, C.c_uint32, C.c_uint32,
+                                                P(TemporalParams), P(C.c_float), P(C.c_float), P(MotionEntry), C.c_uint32,
+                                                P(C.c_float), P(C.c_float), P(C.c_float)]),
+    "rt_temporal_motion_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rt_render_temporal_motion_device": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet),
+                                                   C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams),
+                                                   P(TemporalMotionState), C.c_void_p, C.c_void_p, C.c_void_p, P(Stats)]),
+    "rt_render_temporal_motion": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams), P(TemporalMotionState),
+                                            P(C.c_float), P(C.c_float), P(Stats)]),
 }
 
 HOST_FUNCTIONS = {
@@ -427,6 +462,7 @@ HOST_FUNCTIONS = {
     "rth_load_environment_map": (C.c_int, [C.c_void_p, C.c_char_p]),
     "rth_set_environment_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(V3)]),
     "rth_create_scene_bvh": (C.c_int, [C.c_void_p]),
+    "rth_set_primitive_transform": (C.c_int, [C.c_void_p, C.c_uint32, P(M4x4Inv)]),
     "rth_set_bvh_device": (None, [C.c_int]),
     "rth_build_bvh_entries": (C.c_int, [C.c_uint32, P(V3), P(V3), C.c_int32, P(BvhNode), P(C.c_uint32), P(C.c_uint32)]),
     "rth_scene_desc": (P(SceneDesc), [C.c_void_p]),

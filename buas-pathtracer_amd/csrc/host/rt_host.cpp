@@ -859,6 +859,21 @@ int rth_create_scene_bvh(rth_scene* s) {                                      //
     return 1;
 }
 
+int rth_set_primitive_transform(rth_scene* s, uint32_t primitive_id, const rt_m4x4inv* transform) {
+    if (!s || !transform) { set_err("rth_set_primitive_transform: null argument"); return 0; }
+    if (primitive_id == 0 || primitive_id >= s->primitives.size()) {
+        set_err("rth_set_primitive_transform: primitive id out of range"); return 0;
+    }
+    rt_primitive& p = s->primitives[primitive_id];
+    if (p.transform_index == 0) {                      // the shared identity_transform stays as it is
+        p.transform_index = (uint32_t)s->transforms.size();
+        s->transforms.push_back(*transform);
+    } else {
+        s->transforms[p.transform_index] = *transform;
+    }
+    return 1;
+}
+
 const rt_scene_desc* rth_scene_desc(rth_scene* s) {
     s->mesh_descs.resize(s->meshes.size());
     for (size_t i = 0; i < s->meshes.size(); ++i) {

@@ -4055,6 +4055,23 @@ struct rt_scene {
     uint32_t recurse_grid = 0;          // persistent k_recurse blocks (<= trace_grid*TB/DTB: the spill area)
     V3 ambient = {0, 0, 0};             // Scene::ambient_light (RT/scene.h:102), read by Whitted only
     uint2* gbuf_spill = nullptr;        // k_gbuffer's traversal spill area (GB_MAX_GRID blocks), from the first rt_gbuffer_device on
+    // What derive_instance_tables needs of the upload beside a desc's transform-dependent part (host copies):
+    // rt_scene_update_instances reads no mesh, material or sky array of its desc.
+    struct Keep {
+        std::vector<rt_material> mats;          // with `air`: the blob's segment
+        std::vector<rt_primitive> prims, planes;
+        std::vector<uint32_t> lights;
+        std::vector<DevMesh> meshes;            // offsets
+        std::vector<uint32_t> root4;            // per mesh: the BVH4 root's record
+        std::vector<rt_bvh_node> mesh_root;     // per mesh: nodes[0] (the root box), zero without nodes
+        std::vector<uint32_t> mesh_nodes;       // per mesh: node_count
+        uint32_t mesh_depth = 0, mesh_depth_ref = 0;
+        bool mesh_within = true;                // every mesh node box within 2^40 of the origin
+        long long top_prologue = 1, mlist = 0, lds_scene = 1;   // RT_TOP_PROLOGUE, RT_MLIST_MAX, RT_LDS_SCENE at upload
+        std::vector<rt_m4x4inv> resolved;       // per primitive: transforms[transform_index] (rt_scene_primitive_transforms)
+        static constexpr int TABLES = 9;        // install_instance_tables' tables
+        size_t table_bytes[TABLES] = {};        // and the bytes each one's allocation holds
+    } keep;
 };
 
 namespace {
@@ -5065,6 +5082,207 @@ bool config_from_env(rt_scene_config& c) {
     return ok;
 }
 
+// Everything of a scene that depends on its transforms, its primitives' transform indices and its top-level BVH,
+// on the host: what rt_scene_upload installs first and rt_scene_update_instances replaces.
+struct InstanceTables {
+    std::vector<M34> inv, fwd;
+    std::vector<rt_bvh_node> top_src, top;      // the caller's layout (padded) and the traversal layout
+    uint32_t root_rec = 0;
+    std::vector<float4> seq;                    // the prologue's sequences, or empty
+    uint32_t seq_len = 0, listed_only = 0, finite_boxes = 0;
+    std::vector<float4> rec;                    // the top-level leaf records
+    std::vector<uint8_t> blob;                  // the small tables (scene_in_lds)
+    uint32_t off[BLOB_COUNT] = {};
+    bool blob_fits = false;
+    uint32_t bvh_depth = 0, bvh_depth_ref = 0;
+    std::vector<rt_m4x4inv> resolved;
+};
+
+// finite_box_ray's condition on one node: the box within 2^40 of the origin (NaN fails too)
+bool box_within(const rt_bvh_node& n) {
+    const float c[3] = {n.bv_p.x, n.bv_p.y, n.bv_p.z}, r[3] = {n.bv_r.x, n.bv_r.y, n.bv_r.z};
+    for (int k = 0; k < 3; ++k)
+        if (!(std::fabs(c[k]) + std::fabs(r[k]) <= 1099511627776.0f)) return false;
+    return true;
+}
+
+// One derivation for both entries, so they cannot drift: the index and range checks, the depth bounds, and every
+// table above.  Reads of `d`: the counts, primitives, planes, lights, transforms, bvh_nodes and bvh_indices;
+// the meshes, materials and sky come from `k`.  Touches no device.
+int derive_instance_tables(const char* entry, const rt_scene_desc* d, const rt_scene::Keep& k, const rt_scene_config& cfg,
+                           InstanceTables& t) {
+    for (uint32_t i = 0; i < d->primitive_count; ++i) {
+        const rt_primitive& p = d->primitives[i];
+        if (p.transform_index >= d->transform_count || p.material_id >= d->material_count ||
+            (p.type == RT_PRIMITIVE_MESH && p.mesh_index >= d->mesh_count)) {
+            set_error("primitive references out of range"); return RT_ERROR_INVALID;
+        }
+    }
+    for (uint32_t i = 0; i < d->plane_count; ++i)
+        if (d->planes[i].transform_index >= d->transform_count || d->planes[i].material_id >= d->material_count) {
+            set_error("plane references out of range"); return RT_ERROR_INVALID;
+        }
+    for (uint32_t i = 0; i < d->light_count; ++i)
+        if (d->lights[i] >= d->primitive_count) { set_error("light id out of range"); return RT_ERROR_INVALID; }
+    t.inv.resize(d->transform_count); t.fwd.resize(d->transform_count);
+    for (uint32_t i = 0; i < d->transform_count; ++i)
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) { t.inv[i].e[r][c] = d->transforms[i].inverse.e[r][c]; t.fwd[i].e[r][c] = d->transforms[i].forward.e[r][c]; }
+    const uint32_t top_depth = tree_depth(d->bvh_nodes, d->bvh_node_count);
+    for (uint32_t i = 0; i < d->bvh_index_count; ++i)
+        if (d->bvh_indices[i] >= d->primitive_count) { set_error("bvh index out of range"); return RT_ERROR_INVALID; }
+    // node, triangle and leaf-record arrays get FETCH_Q float4 of padding: a traversal
+    // step loads FETCH_Q float4 unconditionally
+    t.top_src.assign(d->bvh_nodes, d->bvh_nodes + d->bvh_node_count);
+    t.top_src.resize(t.top_src.size() + (FETCH_Q*16 + 31)/32, rt_bvh_node{});
+    t.top = traversal_layout(t.top_src.data(), (uint32_t)t.top_src.size());
+    t.root_rec = t.top[0].left_first;
+    if (k.top_prologue) t.seq = top_sequences(d->bvh_nodes, d->bvh_node_count, d->bvh_index_count, t.seq_len);
+    if (t.seq.empty()) t.seq_len = 0;
+    {
+        uint32_t mesh_slots = 0;
+        for (uint32_t j = 0; j < d->bvh_index_count; ++j)
+            mesh_slots += d->primitives[d->bvh_indices[j]].type == RT_PRIMITIVE_MESH ? 1u : 0u;
+        t.listed_only = (!t.seq.empty() && mesh_slots <= (uint32_t)k.mlist) ? 1u : 0u;
+    }
+    {   // finite_box_ray's scene condition: every box within 2^40 of the origin
+        bool within = k.mesh_within;
+        for (uint32_t i = 0; i < d->bvh_node_count && within; ++i) within = box_within(d->bvh_nodes[i]);
+        t.finite_boxes = within ? 1u : 0u;
+    }
+    if (top_depth + k.mesh_depth + 2 > STACK_DEPTH) {
+        // the device's own bound: a BVH4 level can hold 3 entries where the BVH2's two levels hold 2, so a
+        // BVH2 that the reference's node_stack[64] (RT/intersection.cpp:445) walks may be refused here
+        char msg[256];
+        snprintf(msg, sizeof(msg), "%s: BVH too deep for the device's BVH4 traversal stack: needs %u entries "
+                 "(top level %u + mesh BVH4 %u + 2), %d available (the device's bound, not the reference's BVH2 stack)",
+                 entry, top_depth + k.mesh_depth + 2, top_depth, k.mesh_depth, STACK_DEPTH);
+        set_error(msg);
+        return RT_ERROR_INVALID;
+    }
+    t.bvh_depth = top_depth + k.mesh_depth;
+    t.bvh_depth_ref = top_depth + std::max(k.mesh_depth, k.mesh_depth_ref);
+    if (cfg.traversal_ref && t.bvh_depth_ref + 2 > STACK_DEPTH) {       // RT_TRAVERSAL_REF
+        set_error(std::string(entry) + ": traversal_ref needs more than the 64-entry traversal stack for this BVH");
+        return RT_ERROR_INVALID;
+    }
+    {   // top-level leaf records, in bvh_indices order
+        auto u2f = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
+        t.rec.assign((size_t)d->bvh_index_count*LEAF_REC_Q, make_float4(0, 0, 0, 0));
+        for (uint32_t j = 0; j < d->bvh_index_count; ++j) {
+            const uint32_t pi = d->bvh_indices[j];
+            const rt_primitive& p = d->primitives[pi];
+            float4* q = t.rec.data() + (size_t)j*LEAF_REC_Q;
+            const M34& iv = t.inv[p.transform_index];
+            for (int r = 0; r < 3; ++r) q[r] = make_float4(iv.e[r][0], iv.e[r][1], iv.e[r][2], iv.e[r][3]);
+            bool translate = std::isfinite(iv.e[0][3]) && std::isfinite(iv.e[1][3]) && std::isfinite(iv.e[2][3]);
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 3; ++c) translate = translate && iv.e[r][c] == (r == c ? 1.0f : 0.0f);
+            const uint32_t tword = p.type | (translate ? LEAF_TRANSLATE : 0u);
+            if (p.type == RT_PRIMITIVE_MESH) {
+                const rt_bvh_node& rn = k.mesh_root[p.mesh_index];
+                const uint32_t root = k.root4[p.mesh_index];
+                q[3] = make_float4(u2f(pi), u2f(tword), u2f(k.meshes[p.mesh_index].node_offset), u2f(k.meshes[p.mesh_index].tri_offset));
+                q[4] = make_float4(u2f(root), rn.bv_p.x, rn.bv_p.y, rn.bv_p.z);
+                // q5.w: the mesh has a BVH.  Without one the reference tests none of its triangles
+                // (intersect_mesh, RT/intersection.cpp:259: `if (bvh)`): the root box is made empty
+                // (half sides -1: no slab test passes), and the reference-unit walk counts no root pop
+                if (k.mesh_nodes[p.mesh_index]) q[5] = make_float4(rn.bv_r.x, rn.bv_r.y, rn.bv_r.z, 1.0f);
+                else q[5] = make_float4(-1.0f, -1.0f, -1.0f, 0.0f);
+            } else {
+                q[3] = make_float4(u2f(pi), u2f(tword), p.p[0], p.p[1]);
+                q[4] = make_float4(p.p[2], 0.0f, 0.0f, 0.0f);
+            }
+        }
+        t.rec.resize(t.rec.size() + FETCH_Q, make_float4(0, 0, 0, 0));
+    }
+    {   // the LDS blob (scene_in_lds): the small tables, 16-byte aligned, when they fit
+        auto put = [&](int which, const void* p, size_t bytes) {
+            t.off[which] = (uint32_t)t.blob.size();
+            if (bytes) t.blob.insert(t.blob.end(), (const uint8_t*)p, (const uint8_t*)p + bytes);
+            t.blob.resize((t.blob.size() + 15) & ~(size_t)15, 0);
+        };
+        put(BLOB_MATERIALS, k.mats.data(), k.mats.size()*sizeof(rt_material));
+        put(BLOB_PRIMS, d->primitives, (size_t)d->primitive_count*sizeof(rt_primitive));
+        put(BLOB_PLANES, d->planes, (size_t)d->plane_count*sizeof(rt_primitive));
+        put(BLOB_INV, t.inv.data(), t.inv.size()*sizeof(M34));
+        put(BLOB_FWD, t.fwd.data(), t.fwd.size()*sizeof(M34));
+        put(BLOB_LIGHTS, d->lights, (size_t)d->light_count*sizeof(uint32_t));
+        // the prologue reads the top-level sequences and leaf records from HBM through the scalar
+        // cache, and the strata table stays in HBM (both read through L2): not copied into LDS
+        put(BLOB_MESHES, k.meshes.data(), k.meshes.size()*sizeof(DevMesh));
+        t.blob_fits = t.blob.size() <= 16*(size_t)LDS_SCENE_Q && k.lds_scene;
+    }
+    t.resolved.resize(d->primitive_count);
+    for (uint32_t i = 0; i < d->primitive_count; ++i) t.resolved[i] = d->transforms[d->primitives[i].transform_index];
+    return RT_OK;
+}
+
+// The derived tables onto the device, in place of the scene's (none at the first call).  A table that fits the
+// allocation it has is overwritten there (an update of the same shape costs nine copies and no hipMalloc or
+// hipFree); one that does not gets a new allocation, and every new allocation is made before a byte of the scene
+// changes, so running out of memory leaves the scene as it was.  The caller has synchronised the device.
+int install_instance_tables(rt_scene* s, const rt_scene_desc* d, InstanceTables& t) {
+    DevScene& ds = s->ds;
+    std::vector<float4> blob_q;
+    if (t.blob_fits) {
+        blob_q.resize(t.blob.size() / 16);
+        memcpy(blob_q.data(), t.blob.data(), t.blob.size());
+    }
+    auto each = [&](auto&& f) {
+        f(0, ds.prims, d->primitives, (size_t)d->primitive_count);
+        f(1, ds.inv, t.inv.data(), t.inv.size());
+        f(2, ds.fwd, t.fwd.data(), t.fwd.size());
+        f(3, ds.bvh_src, t.top_src.data(), t.top_src.size());
+        f(4, ds.bvh, t.top.data(), t.top.size());
+        f(5, ds.bvh_idx, d->bvh_indices, (size_t)d->bvh_index_count);
+        f(6, ds.top_seq, t.seq.data(), t.seq.size());
+        f(7, ds.leaf_rec, t.rec.data(), t.rec.size());
+        f(8, ds.blob, blob_q.data(), blob_q.size());
+    };
+    size_t* cap = s->keep.table_bytes;
+    void* fresh[rt_scene::Keep::TABLES] = {};
+    int err = RT_OK;
+    each([&](int i, auto*& field, auto* host, size_t count) {
+        const size_t bytes = count*sizeof(*host);
+        if (err || !bytes || (field && bytes <= cap[i])) return;
+        if (hipMalloc(&fresh[i], bytes) != hipSuccess) { set_error("hipMalloc of a scene table"); err = RT_ERROR_OUT_OF_MEMORY; }
+    });
+    if (err) {
+        for (void* p : fresh) if (p) (void)hipFree(p);
+        return err;
+    }
+    each([&](int i, auto*& field, auto* host, size_t count) {
+        using T = std::remove_reference_t<decltype(field)>;
+        const size_t bytes = count*sizeof(*host);
+        if (fresh[i] || !bytes) {                       // the old allocation goes
+            void* old = const_cast<void*>(static_cast<const void*>(field));
+            auto it = std::find(s->allocs.begin(), s->allocs.end(), old);
+            if (old && it != s->allocs.end()) { (void)hipFree(old); s->allocs.erase(it); }
+            field = static_cast<T>(fresh[i]);
+            if (fresh[i]) s->allocs.push_back(fresh[i]);
+            cap[i] = bytes;
+        }
+        if (bytes && hipMemcpy(const_cast<void*>(static_cast<const void*>(field)), host, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("hipMemcpy of a scene table"); err = RT_ERROR_DEVICE;
+        }
+    });
+    if (err) return err;
+    ds.blob_q = (uint32_t)blob_q.size();
+    ds.bvh_root_rec = t.root_rec;
+    ds.top_seq_len = t.seq_len;
+    ds.mlist_max = (uint32_t)s->keep.mlist;
+    ds.listed_only = t.listed_only;
+    ds.finite_boxes = t.finite_boxes;
+    ds.bvh_node_count = d->bvh_node_count;
+    for (int i = 0; i < BLOB_COUNT; ++i) ds.off[i] = t.off[i];
+    s->bvh_depth = t.bvh_depth;
+    s->bvh_depth_ref = t.bvh_depth_ref;
+    s->keep.prims.assign(d->primitives, d->primitives + d->primitive_count);
+    s->keep.resolved.swap(t.resolved);
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -5214,70 +5432,15 @@ int rt_scene_upload(const rt_scene_desc* d, int device, rt_scene** out) {
     ds.material_count = d->material_count;
     ds.air_id = d->material_count;
     if ((err = upload(s, mats.data(), mats.size(), &ds.materials))) return fail(err);
-    for (uint32_t i = 0; i < d->primitive_count; ++i) {
-        const rt_primitive& p = d->primitives[i];
-        if (p.transform_index >= d->transform_count || p.material_id >= d->material_count ||
-            (p.type == RT_PRIMITIVE_MESH && p.mesh_index >= d->mesh_count)) {
-            set_error("primitive references out of range"); return fail(RT_ERROR_INVALID);
-        }
-    }
-    for (uint32_t i = 0; i < d->plane_count; ++i)
-        if (d->planes[i].transform_index >= d->transform_count || d->planes[i].material_id >= d->material_count) {
-            set_error("plane references out of range"); return fail(RT_ERROR_INVALID);
-        }
-    for (uint32_t i = 0; i < d->light_count; ++i)
-        if (d->lights[i] >= d->primitive_count) { set_error("light id out of range"); return fail(RT_ERROR_INVALID); }
-    if ((err = upload(s, d->primitives, d->primitive_count, &ds.prims))) return fail(err);
-    if ((err = upload(s, d->planes, d->plane_count, &ds.planes))) return fail(err);
-    {   // the prologue's plane table: p[0..3] per plane, four per scalar load
-        std::vector<float4> nd((d->plane_count + 3u) / 4u * 4u + 4u, make_float4(0, 0, 0, 0));
-        for (uint32_t i = 0; i < d->plane_count; ++i)
-            nd[i] = make_float4(d->planes[i].p[0], d->planes[i].p[1], d->planes[i].p[2], d->planes[i].p[3]);
-        if ((err = upload(s, nd.data(), nd.size(), &ds.plane_nd))) return fail(err);
-    }
-    ds.plane_count = d->plane_count;
-    std::vector<M34> inv(d->transform_count), fwd(d->transform_count);
-    for (uint32_t i = 0; i < d->transform_count; ++i)
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 4; ++c) { inv[i].e[r][c] = d->transforms[i].inverse.e[r][c]; fwd[i].e[r][c] = d->transforms[i].forward.e[r][c]; }
-    if ((err = upload(s, inv.data(), inv.size(), &ds.inv))) return fail(err);
-    if ((err = upload(s, fwd.data(), fwd.size(), &ds.fwd))) return fail(err);
-    if ((err = upload(s, d->lights, d->light_count, &ds.lights))) return fail(err);
-    ds.light_count = d->light_count;
-    uint32_t top_depth = tree_depth(d->bvh_nodes, d->bvh_node_count);
-    for (uint32_t i = 0; i < d->bvh_index_count; ++i)
-        if (d->bvh_indices[i] >= d->primitive_count) { set_error("bvh index out of range"); return fail(RT_ERROR_INVALID); }
-    // node, triangle and leaf-record arrays get FETCH_Q float4 of padding: a traversal
-    // step loads FETCH_Q float4 unconditionally
-    std::vector<rt_bvh_node> top_nodes(d->bvh_nodes, d->bvh_nodes + d->bvh_node_count);
-    top_nodes.resize(top_nodes.size() + (FETCH_Q*16 + 31)/32, rt_bvh_node{});
-    if ((err = upload(s, top_nodes.data(), top_nodes.size(), &ds.bvh_src))) return fail(err);
-    {
-        std::vector<rt_bvh_node> tl = traversal_layout(top_nodes.data(), (uint32_t)top_nodes.size());
-        ds.bvh_root_rec = tl[0].left_first;
-        if ((err = upload(s, tl.data(), tl.size(), &ds.bvh))) return fail(err);
-    }
-    if ((err = upload(s, d->bvh_indices, d->bvh_index_count, &ds.bvh_idx))) return fail(err);
-    {
+    {   // the switches of the derived tables, read once: an update derives under the upload's
         bool env_ok = true;
-        long long top = 1, mlist = MLIST_MAX;
+        long long top = 1, mlist = MLIST_MAX, lds_scene = 1;
         env_int("rt_scene_upload", "RT_TOP_PROLOGUE", 0, 1, top, env_ok);   // 0: the trace kernels walk the top level
         env_int("rt_scene_upload", "RT_MLIST_MAX", 0, MLIST_MAX, mlist, env_ok);
+        env_int("rt_scene_upload", "RT_LDS_SCENE", 0, 1, lds_scene, env_ok);   // 0: the kernels read the tables from HBM
         if (!env_ok) return fail(RT_ERROR_INVALID);
-        std::vector<float4> seq;
-        uint32_t len = 0;
-        if (top) seq = top_sequences(d->bvh_nodes, d->bvh_node_count, d->bvh_index_count, len);
-        ds.top_seq = nullptr; ds.top_seq_len = 0; ds.mlist_max = (uint32_t)mlist;
-        if (!seq.empty()) {
-            if ((err = upload(s, seq.data(), seq.size(), &ds.top_seq))) return fail(err);
-            ds.top_seq_len = len;
-        }
-        uint32_t mesh_slots = 0;
-        for (uint32_t j = 0; j < d->bvh_index_count; ++j)
-            mesh_slots += d->primitives[d->bvh_indices[j]].type == RT_PRIMITIVE_MESH ? 1u : 0u;
-        ds.listed_only = (ds.top_seq && mesh_slots <= ds.mlist_max) ? 1u : 0u;
+        s->keep.top_prologue = top; s->keep.mlist = mlist; s->keep.lds_scene = lds_scene;
     }
-    ds.bvh_node_count = d->bvh_node_count;
     // meshes: concatenate, triangles as (a, b-a, c-a) float4 triples
     std::vector<DevMesh> meshes(d->mesh_count);
     std::vector<float4> tris;
@@ -5334,66 +5497,36 @@ int rt_scene_upload(const rt_scene_desc* d, int device, rt_scene** out) {
         mnodes.insert(mnodes.end(), M.nodes, M.nodes + M.node_count);
         mesh4.push_back((uint32_t)(mnodes4.size() / 8));
     }
-    {   // finite_box_ray's scene condition: every box within 2^40 of the origin
-        auto within = [](const rt_bvh_node* n, size_t count) {
-            for (size_t i = 0; i < count; ++i) {
-                const float c[3] = {n[i].bv_p.x, n[i].bv_p.y, n[i].bv_p.z}, r[3] = {n[i].bv_r.x, n[i].bv_r.y, n[i].bv_r.z};
-                for (int k = 0; k < 3; ++k)
-                    if (!(std::fabs(c[k]) + std::fabs(r[k]) <= 1099511627776.0f)) return false;   // NaN fails too
-            }
-            return true;
-        };
-        ds.finite_boxes = (within(d->bvh_nodes, d->bvh_node_count) && within(mnodes.data(), mnodes.size())) ? 1u : 0u;
-    }
-    if (top_depth + mesh_depth + 2 > STACK_DEPTH) {
-        // the device's own bound: a BVH4 level can hold 3 entries where the BVH2's two levels hold 2, so a
-        // BVH2 that the reference's node_stack[64] (RT/intersection.cpp:445) walks may be refused here
-        char msg[224];
-        snprintf(msg, sizeof(msg), "rt_scene_upload: BVH too deep for the device's BVH4 traversal stack: needs %u entries "
-                 "(top level %u + mesh BVH4 %u + 2), %d available (the device's bound, not the reference's BVH2 stack)",
-                 top_depth + mesh_depth + 2, top_depth, mesh_depth, STACK_DEPTH);
-        set_error(msg);
-        return fail(RT_ERROR_INVALID);
-    }
-    s->bvh_depth = top_depth + mesh_depth;
-    s->bvh_depth_ref = top_depth + std::max(mesh_depth, mesh_depth_ref);
-    if (s->cfg.traversal_ref && s->bvh_depth_ref + 2 > STACK_DEPTH) {       // RT_TRAVERSAL_REF
-        set_error("rt_scene_upload: traversal_ref needs more than the 64-entry traversal stack for this BVH");
-        return fail(RT_ERROR_INVALID);
-    }
-    {   // top-level leaf records, in bvh_indices order
-        auto u2f = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
-        std::vector<float4> rec((size_t)d->bvh_index_count*LEAF_REC_Q, make_float4(0, 0, 0, 0));
-        for (uint32_t j = 0; j < d->bvh_index_count; ++j) {
-            const uint32_t pi = d->bvh_indices[j];
-            const rt_primitive& p = d->primitives[pi];
-            float4* q = rec.data() + (size_t)j*LEAF_REC_Q;
-            const M34& iv = inv[p.transform_index];
-            for (int r = 0; r < 3; ++r) q[r] = make_float4(iv.e[r][0], iv.e[r][1], iv.e[r][2], iv.e[r][3]);
-            bool translate = std::isfinite(iv.e[0][3]) && std::isfinite(iv.e[1][3]) && std::isfinite(iv.e[2][3]);
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 3; ++c) translate = translate && iv.e[r][c] == (r == c ? 1.0f : 0.0f);
-            const uint32_t tword = p.type | (translate ? LEAF_TRANSLATE : 0u);
-            if (p.type == RT_PRIMITIVE_MESH) {
-                const rt_mesh& M = d->meshes[p.mesh_index];
-                rt_bvh_node rn = {};
-                if (M.node_count) rn = M.nodes[0];
-                const uint32_t root = root4[p.mesh_index];
-                q[3] = make_float4(u2f(pi), u2f(tword), u2f(meshes[p.mesh_index].node_offset), u2f(meshes[p.mesh_index].tri_offset));
-                q[4] = make_float4(u2f(root), rn.bv_p.x, rn.bv_p.y, rn.bv_p.z);
-                // q5.w: the mesh has a BVH.  Without one the reference tests none of its triangles
-                // (intersect_mesh, RT/intersection.cpp:259: `if (bvh)`): the root box is made empty
-                // (half sides -1: no slab test passes), and the reference-unit walk counts no root pop
-                if (M.node_count) q[5] = make_float4(rn.bv_r.x, rn.bv_r.y, rn.bv_r.z, 1.0f);
-                else q[5] = make_float4(-1.0f, -1.0f, -1.0f, 0.0f);
-            } else {
-                q[3] = make_float4(u2f(pi), u2f(tword), p.p[0], p.p[1]);
-                q[4] = make_float4(p.p[2], 0.0f, 0.0f, 0.0f);
-            }
+    {   // what the derivation needs of the meshes, kept for rt_scene_update_instances
+        rt_scene::Keep& k = s->keep;
+        k.mats = mats;
+        k.meshes = meshes;
+        k.root4 = root4;
+        k.mesh_root.assign(d->mesh_count, rt_bvh_node{});
+        k.mesh_nodes.assign(d->mesh_count, 0u);
+        for (uint32_t m = 0; m < d->mesh_count; ++m) {
+            k.mesh_nodes[m] = d->meshes[m].node_count;
+            if (d->meshes[m].node_count) k.mesh_root[m] = d->meshes[m].nodes[0];
         }
-        rec.resize(rec.size() + FETCH_Q, make_float4(0, 0, 0, 0));
-        if ((err = upload(s, rec.data(), rec.size(), &ds.leaf_rec))) return fail(err);
+        k.mesh_depth = mesh_depth; k.mesh_depth_ref = mesh_depth_ref;
+        k.mesh_within = true;
+        for (size_t i = 0; i < mnodes.size() && k.mesh_within; ++i) k.mesh_within = box_within(mnodes[i]);
     }
+    InstanceTables it;
+    if ((err = derive_instance_tables("rt_scene_upload", d, s->keep, s->cfg, it))) return fail(err);
+    if ((err = upload(s, d->planes, d->plane_count, &ds.planes))) return fail(err);
+    {   // the prologue's plane table: p[0..3] per plane, four per scalar load
+        std::vector<float4> nd((d->plane_count + 3u) / 4u * 4u + 4u, make_float4(0, 0, 0, 0));
+        for (uint32_t i = 0; i < d->plane_count; ++i)
+            nd[i] = make_float4(d->planes[i].p[0], d->planes[i].p[1], d->planes[i].p[2], d->planes[i].p[3]);
+        if ((err = upload(s, nd.data(), nd.size(), &ds.plane_nd))) return fail(err);
+    }
+    ds.plane_count = d->plane_count;
+    if ((err = upload(s, d->lights, d->light_count, &ds.lights))) return fail(err);
+    ds.light_count = d->light_count;
+    s->keep.planes.assign(d->planes, d->planes + d->plane_count);
+    s->keep.lights.assign(d->lights, d->lights + d->light_count);
+    if ((err = install_instance_tables(s, d, it))) return fail(err);
     if ((err = upload(s, meshes.data(), meshes.size(), &ds.meshes))) return fail(err);
     tris.resize(tris.size() + FETCH_Q, make_float4(0, 0, 0, 0));
     if ((err = upload(s, tris.data(), tris.size(), &ds.tris))) return fail(err);
@@ -5458,38 +5591,10 @@ int rt_scene_upload(const rt_scene_desc* d, int device, rt_scene** out) {
     ds.bot_sky = rv3(d->bot_sky_color);
     if ((err = upload(s, rt_dev_strata_tab, sizeof(rt_dev_strata_tab), &ds.strata))) return fail(err);
     if ((err = upload(s, rt_dev_bluenoise_tab, sizeof(rt_dev_bluenoise_tab), &ds.bluenoise))) return fail(err);
-    {   // the LDS blob (scene_in_lds): the small tables, 16-byte aligned, when they fit
-        std::vector<uint8_t> blob;
-        auto put = [&](int which, const void* p, size_t bytes) {
-            ds.off[which] = (uint32_t)blob.size();
-            if (bytes) blob.insert(blob.end(), (const uint8_t*)p, (const uint8_t*)p + bytes);
-            blob.resize((blob.size() + 15) & ~(size_t)15, 0);
-        };
-        put(BLOB_MATERIALS, mats.data(), mats.size()*sizeof(rt_material));
-        put(BLOB_PRIMS, d->primitives, (size_t)d->primitive_count*sizeof(rt_primitive));
-        put(BLOB_PLANES, d->planes, (size_t)d->plane_count*sizeof(rt_primitive));
-        put(BLOB_INV, inv.data(), inv.size()*sizeof(M34));
-        put(BLOB_FWD, fwd.data(), fwd.size()*sizeof(M34));
-        put(BLOB_LIGHTS, d->lights, (size_t)d->light_count*sizeof(uint32_t));
-        // the prologue reads the top-level sequences and leaf records from HBM through the scalar
-        // cache, and the strata table stays in HBM (both read through L2): not copied into LDS
-        put(BLOB_MESHES, meshes.data(), meshes.size()*sizeof(DevMesh));
-        bool env_ok = true;
-        long long lds_scene = 1;                                 // 0: the kernels read the tables from HBM
-        env_int("rt_scene_upload", "RT_LDS_SCENE", 0, 1, lds_scene, env_ok);
-        if (!env_ok) return fail(RT_ERROR_INVALID);
-        ds.blob = nullptr; ds.blob_q = 0;
-        if (blob.size() <= 16*(size_t)LDS_SCENE_Q && lds_scene) {
-            std::vector<float4> q(blob.size() / 16);
-            memcpy(q.data(), blob.data(), blob.size());
-            if ((err = upload(s, q.data(), q.size(), &ds.blob))) return fail(err);
-            ds.blob_q = (uint32_t)q.size();
-        }
-        if (debug_timing())
-            fprintf(stderr, "[rt timing] rt_scene_upload: scene tables %zu B (%s LDS; materials %zu, primitives %u, planes %u, "
-                    "transforms %zu, lights %u, meshes %zu)\n", blob.size(), ds.blob_q ? "in" : "not in", mats.size(),
-                    d->primitive_count, d->plane_count, inv.size(), d->light_count, meshes.size());
-    }
+    if (debug_timing())
+        fprintf(stderr, "[rt timing] rt_scene_upload: scene tables %zu B (%s LDS; materials %zu, primitives %u, planes %u, "
+                "transforms %zu, lights %u, meshes %zu)\n", it.blob.size(), ds.blob_q ? "in" : "not in", mats.size(),
+                d->primitive_count, d->plane_count, it.inv.size(), d->light_count, meshes.size());
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) != hipSuccess) { set_error("hipGetDeviceProperties"); return fail(RT_ERROR_DEVICE); }
@@ -5531,6 +5636,60 @@ int rt_scene_upload(const rt_scene_desc* d, int device, rt_scene** out) {
     if (ensure_partition(s, 0)) return fail(RT_ERROR_OUT_OF_MEMORY);
     if (hipMalloc(&s->d_lut, 512*sizeof(float)) != hipSuccess) { set_error("hipMalloc lut"); return fail(RT_ERROR_OUT_OF_MEMORY); }
     *out = s;
+    return RT_OK;
+}
+
+int rt_scene_update_instances(rt_scene* s, const rt_scene_desc* d) {
+    const std::string e = "rt_scene_update_instances";
+    if (!s) { set_error(e + ": null scene"); return RT_ERROR_INVALID; }
+    if (!d) { set_error(e + ": null desc"); return RT_ERROR_INVALID; }
+    const rt_scene::Keep& k = s->keep;
+    // what must match the upload, by name
+    if (d->material_count != s->ds.material_count) { set_error(e + ": material_count differs from the uploaded scene's"); return RT_ERROR_INVALID; }
+    if (d->primitive_count != k.prims.size()) { set_error(e + ": primitive_count differs from the uploaded scene's"); return RT_ERROR_INVALID; }
+    if (d->plane_count != k.planes.size()) { set_error(e + ": plane_count differs from the uploaded scene's"); return RT_ERROR_INVALID; }
+    if (d->light_count != k.lights.size()) { set_error(e + ": light_count differs from the uploaded scene's"); return RT_ERROR_INVALID; }
+    if (d->mesh_count != k.meshes.size()) { set_error(e + ": mesh_count differs from the uploaded scene's"); return RT_ERROR_INVALID; }
+    if (d->primitive_count && !d->primitives) { set_error(e + ": null primitives"); return RT_ERROR_INVALID; }
+    if (d->plane_count && !d->planes) { set_error(e + ": null planes"); return RT_ERROR_INVALID; }
+    if (d->light_count && !d->lights) { set_error(e + ": null lights"); return RT_ERROR_INVALID; }
+    if (d->transform_count && !d->transforms) { set_error(e + ": null transforms"); return RT_ERROR_INVALID; }
+    if (d->bvh_node_count && !d->bvh_nodes) { set_error(e + ": null bvh_nodes"); return RT_ERROR_INVALID; }
+    if (d->bvh_index_count && !d->bvh_indices) { set_error(e + ": null bvh_indices"); return RT_ERROR_INVALID; }
+    for (uint32_t i = 0; i < d->primitive_count; ++i) {
+        const rt_primitive& a = d->primitives[i];
+        const rt_primitive& b = k.prims[i];
+        const char* what = a.type != b.type ? "type" : a.material_id != b.material_id ? "material_id"
+                           : a.mesh_index != b.mesh_index ? "mesh_index" : memcmp(a.p, b.p, sizeof(a.p)) ? "p" : nullptr;
+        if (what) {
+            set_error(e + ": primitive " + std::to_string(i) + ": " + what + " differs from the uploaded scene's");
+            return RT_ERROR_INVALID;
+        }
+    }
+    if (d->plane_count && memcmp(d->planes, k.planes.data(), sizeof(rt_primitive)*(size_t)d->plane_count)) {
+        set_error(e + ": planes differ from the uploaded scene's"); return RT_ERROR_INVALID;
+    }
+    if (d->light_count && memcmp(d->lights, k.lights.data(), sizeof(uint32_t)*(size_t)d->light_count)) {
+        set_error(e + ": lights differ from the uploaded scene's"); return RT_ERROR_INVALID;
+    }
+    // the upload's own checks and tables, from the same text
+    InstanceTables it;
+    int err = derive_instance_tables(e.c_str(), d, k, s->cfg, it);
+    if (err) return err;
+    // the device from here on: no frame of the scene may still read a table that goes
+    if ((err = bind_device(s->device))) return err;
+    HIP_OK(hipDeviceSynchronize());
+    return install_instance_tables(s, d, it);
+}
+
+int rt_scene_primitive_transforms(const rt_scene* s, uint32_t cap, rt_m4x4inv* out, uint32_t* out_count) {
+    if (!s) { set_error("rt_scene_primitive_transforms: null scene"); return RT_ERROR_INVALID; }
+    if (!out_count) { set_error("rt_scene_primitive_transforms: null out_count"); return RT_ERROR_INVALID; }
+    if (cap && !out) { set_error("rt_scene_primitive_transforms: null out with a capacity"); return RT_ERROR_INVALID; }
+    const std::vector<rt_m4x4inv>& r = s->keep.resolved;
+    *out_count = (uint32_t)r.size();
+    const size_t n = std::min((size_t)cap, r.size());
+    if (n) memcpy(out, r.data(), sizeof(rt_m4x4inv)*n);
     return RT_OK;
 }
 

@@ -966,6 +966,98 @@ int rt_render_temporal_filtered(rt_scene* scene, const rt_camera* camera, const 
                                 rt_temporal_filtered_state* state, float* out_pixels, float* out_history,
                                 float* out_length, float* out_variance, rt_stats* stats);
 
+/* Moving instances after upload, and a history that follows them (beyond the reference, an opt-in: new entries
+ * only, no other entry changes; RT_ABI_VERSION stays).  DESIGN.md ("Moving instances") defines the update and the
+ * stage operation by operation; the stage's kernel matches tests/ref_motion/ref_motion.c bit for bit.
+ *
+ * rt_scene_update_instances replaces the transform-dependent tables of an uploaded scene: the transforms, the
+ * top-level BVH with its prologue sequences and leaf records, and the small-table blob.  `desc` must describe the
+ * uploaded scene except for transforms[] (whose count may change), primitives[i].transform_index and the top-level
+ * BVH (bvh_nodes, bvh_indices and their counts).  The counts of materials, primitives, planes, lights and meshes
+ * and each primitive's type, material_id, mesh_index and p[] must equal the uploaded ones (planes and lights are
+ * compared whole): a mismatch is RT_ERROR_INVALID by name.  desc->materials, desc->skydome and the meshes'
+ * triangles / normals / nodes / indices are never read and may be NULL: no mesh, sky or material byte is uploaded
+ * again.  Every check (index ranges, the BVH's depth against the 64-entry traversal stack, traversal_ref's bound)
+ * happens before the device is touched: a refused update leaves the scene exactly as it was.  The entry
+ * synchronises the device before it replaces a table.  After it every entry on the scene is bit-identical to the
+ * same entry on a fresh rt_scene_upload of `desc`; the scene's config, recursive opt-in, ambient light,
+ * partitions and spill areas survive. */
+int rt_scene_update_instances(rt_scene* scene, const rt_scene_desc* desc);
+/* The resolved transform of every primitive (transforms[primitives[i].transform_index]) as of the upload or the
+ * last update, from a host copy: out[0 .. min(cap, count)) and *out_count = the scene's primitive count.  out may
+ * be NULL with cap 0.  No device work. */
+int rt_scene_primitive_transforms(const rt_scene* scene, uint32_t cap, rt_m4x4inv* out, uint32_t* out_count);
+
+/* One primitive's rigid motion between two frames: a world point P of the current frame lies at
+ * fwd_prev * (inv_cur * P) in the previous one (rows 0..2 of the current inverse and of the previous forward). */
+typedef struct rt_motion_entry {   /* 112 B */
+    float    inv_cur[3][4];
+    float    fwd_prev[3][4];
+    uint32_t moved;                /* 1: any of the 24 words of forward rows 0..2 and inverse rows 0..2 differs */
+    uint32_t reserved[3];          /* 0 */
+} rt_motion_entry;
+/* out[i] from cur[i] and prev[i], i < count; the words are compared as integers.  No device needed. */
+int rt_motion_table(uint32_t count, const rt_m4x4inv* cur, const rt_m4x4inv* prev, rt_motion_entry* out);
+
+/* The motion-aware accumulate stage: rt_temporal_accumulate_device's arguments and operations with one new step.
+ * For a hit whose primitive has no RT_HIT_PLANE_BIT, is below motion_count and whose entry has moved != 0:
+ *   Po.k = ((a[k][0]*P.x + a[k][1]*P.y) + a[k][2]*P.z) + a[k][3], a = inv_cur;  Q likewise from Po with fwd_prev;
+ *   m likewise from n through the two 3 x 3 parts (no translation), divided by its length when that is > 0 (else
+ *   m = n);
+ * and Q and m stand where P and n stand in the projection and in the tap tests; plane_limit stays
+ * plane_tolerance * t.  Every other pixel (a miss, a plane, an id >= motion_count, moved == 0, d_motion NULL) takes
+ * rt_temporal_accumulate_device's path word for word.  d_motion NULL requires motion_count 0.
+ * d_moments (w*h float2, optional) receives rt_temporal_accumulate_moments_device's moments; with it and a history
+ * d_prev_moments is required, without it d_prev_moments must be NULL.  d_velocity (w*h float2, optional) receives
+ * (fx - x, fy - y) where the projection into the previous frame succeeds and two quiet NaNs (0x7FC00000) elsewhere:
+ * invalid current pixels and calls without history among them. */
+int rt_temporal_accumulate_motion_device(int device, const float* d_current, const rt_gbuffer_texel* d_gbuffer,
+                                         const float* d_prev_history, const float* d_prev_length,
+                                         const rt_gbuffer_texel* d_prev_gbuffer, const rt_camera* prev_camera,
+                                         float prev_lens_distortion, uint32_t w, uint32_t h,
+                                         const rt_temporal_params* p, float* d_history, float* d_length,
+                                         void* hip_stream, const rt_motion_entry* d_motion, uint32_t motion_count,
+                                         const float* d_prev_moments, float* d_moments, float* d_velocity);
+/* Same on host buffers (motion: motion_count entries on the host). */
+int rt_temporal_accumulate_motion(int device, const float* current, const rt_gbuffer_texel* gbuffer,
+                                  const float* prev_history, const float* prev_length,
+                                  const rt_gbuffer_texel* prev_gbuffer, const rt_camera* prev_camera,
+                                  float prev_lens_distortion, uint32_t w, uint32_t h, const rt_temporal_params* p,
+                                  float* history, float* length, const rt_motion_entry* motion,
+                                  uint32_t motion_count, const float* prev_moments, float* moments, float* velocity);
+
+/* The driver: rt_render_temporal_device's frame with the motion-aware stage, written on the public entries.
+ * `state` is the caller's, all zero but its three pointers at the start: d_workspace
+ * (rt_temporal_motion_workspace_bytes(w, h, the scene's primitive count) bytes on the scene's device:
+ * rt_temporal_workspace_bytes(w, h), then the table) and transforms, a host array of transform_cap entries
+ * (>= the scene's primitive count).  A frame renders into the workspace and writes the G-buffer as
+ * rt_render_temporal_device does, takes the current transforms with rt_scene_primitive_transforms, builds the
+ * table with rt_motion_table against state->transforms and uploads it, runs
+ * rt_temporal_accumulate_motion_device (without history when state->frames is 0, the frame size changed or
+ * state->primitive_count differs from the scene's: the state restarts), copies the history (and the length)
+ * out, and stores the camera and the transforms in the state.  rt_cancel and the refusals are
+ * rt_render_temporal_device's, plus a NULL transforms or a transform_cap below the scene's primitive count. */
+size_t rt_temporal_motion_workspace_bytes(uint32_t w, uint32_t h, uint32_t primitive_count);   /* no device needed */
+typedef struct rt_temporal_motion_state {   /* the caller's */
+    uint32_t   w, h, frames, parity;
+    rt_camera  camera;
+    float      lens_distortion;
+    uint32_t   primitive_count;             /* of the stored transforms */
+    uint32_t   transform_cap;               /* entries `transforms` has room for */
+    void*      d_workspace;
+    rt_m4x4inv* transforms;                 /* host */
+} rt_temporal_motion_state;
+int rt_render_temporal_motion_device(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                                     const rt_filter_cache* filter, const rt_tile_set* tiles,
+                                     uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
+                                     const rt_temporal_params* p, rt_temporal_motion_state* state, float* d_out,
+                                     float* d_length_out, void* hip_stream, rt_stats* stats);
+int rt_render_temporal_motion(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                              const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                              uint32_t w, uint32_t h, uint32_t frame_count, const rt_temporal_params* p,
+                              rt_temporal_motion_state* state, float* out_pixels, float* out_length,
+                              rt_stats* stats);
+
 /* The reference's top-down BVH builders on the device (RT/bvh.cpp:222-326 with
  * partition_midpoint :53-61, partition_sah_binned :138-213 or the full SAH sweep
  * partition_objects_sah / evaluate_sah :63-131, the partition of :26-51): one launch per

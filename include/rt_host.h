@@ -104,6 +104,11 @@ int      rth_build_bvh_entries(uint32_t n, const rt_v3* p, const rt_v3* r, int32
 
 /* create_scene_bvh (binned SAH over primitives 1..n) */
 int      rth_create_scene_bvh(rth_scene* s);
+/* Move a sphere, box or mesh instance (beyond the reference: its scenes are static): primitive `primitive_id`
+ * (not the null primitive 0; planes have no transform) gets `transform`.  One that shares the identity slot gets a
+ * slot of its own.  The top-level BVH is stale until rth_create_scene_bvh is called again; rth_scene_desc then
+ * returns the new desc (for rt_scene_update_instances or a fresh rt_scene_upload).  Returns 0 on a bad id. */
+int      rth_set_primitive_transform(rth_scene* s, uint32_t primitive_id, const rt_m4x4inv* transform);
 /* Flattened view, valid until the scene is modified or destroyed. */
 const rt_scene_desc* rth_scene_desc(rth_scene* s);
 
