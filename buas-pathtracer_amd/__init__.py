@@ -226,6 +226,20 @@ class Scene:
         if not lib().rth_set_primitive_transform(self._h, primitive_id, C.byref(transform)):
             raise ValueError((lib().rth_last_error() or b"").decode())
 
+    def update_mesh(self, mesh_id, triangles, normals=None):
+        """rth_update_mesh: new vertices for a mesh, [n,3,3] in create_mesh's order (normals likewise, or None to keep
+        the stored ones); its BVH is refitted, the topology stays.  Call create_scene_bvh() again before desc() is
+        uploaded or passed to DeviceScene.update_instances."""
+        t = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 3, 3)
+        n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3, 3)
+        d = self.desc()
+        if mesh_id < d.mesh_count and (t.shape[0] != d.meshes[mesh_id].triangle_count or
+                                       (n is not None and n.shape[0] != t.shape[0])):
+            raise ValueError("update_mesh: the mesh's triangle count cannot change")
+        if not lib().rth_update_mesh(self._h, mesh_id, t.ctypes.data_as(C.POINTER(V3)),
+                                     None if n is None else n.ctypes.data_as(C.POINTER(V3))):
+            raise ValueError((lib().rth_last_error() or b"").decode())
+
     def bvh_info(self, mesh_id=None):
         info = BvhInfo()
         if mesh_id is None:
@@ -283,6 +297,58 @@ class DeviceScene:
         if desc is None:
             desc = self.scene.desc()
         _check(lib().rt_scene_update_instances(self._h, C.byref(desc)))
+
+    def _mesh_triangles(self, mesh_index):
+        """The mesh's triangle count, or None for an index the scene refuses (the update entry then says so)."""
+        size = C.c_size_t()
+        if lib().rt_debug_scene_mesh_table(self._h, mesh_index, abi.RT_MESH_TABLE_TRIANGLES, None, 0, C.byref(size)):
+            return None
+        return size.value // 48
+
+    def update_mesh(self, mesh_index, triangles, normals=None):
+        """rt_scene_update_mesh: new vertices for one mesh of the uploaded scene, float32 [n,3,3] in the mesh's
+        original triangle order (normals likewise, or None to keep the stored ones); the mesh's BVH is refitted on the
+        device.  Returns node 0 (abi.BvhNode).  When its box changed, the scene refuses to trace until
+        update_instances() with a top-level BVH over the new bounds: Scene.update_mesh, Scene.create_scene_bvh, then
+        DeviceScene.update_instances."""
+        t = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 3, 3)
+        n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3, 3)
+        count = self._mesh_triangles(mesh_index)
+        if count is not None and (t.shape[0] != count or (n is not None and n.shape[0] != count)):
+            raise ValueError(f"update_mesh: mesh {mesh_index} has {count} triangles")
+        fp = C.POINTER(C.c_float)
+        root = abi.BvhNode()
+        _check(lib().rt_scene_update_mesh(self._h, mesh_index, t.ctypes.data_as(fp),
+                                          None if n is None else n.ctypes.data_as(fp), C.byref(root)))
+        return root
+
+    def update_mesh_device(self, mesh_index, d_triangles, d_normals=None):
+        """rt_scene_update_mesh_device: the same from device memory, as pointers (9 float32 per triangle, original
+        order) or as contiguous float32 torch tensors on the scene's device."""
+        count = self._mesh_triangles(mesh_index)
+
+        def ptr(x):
+            if x is None or isinstance(x, int):
+                return x
+            if str(x.dtype) != "torch.float32" or not x.is_contiguous() or (count is not None and x.numel() != 9*count):
+                raise ValueError(f"update_mesh_device: a contiguous float32 tensor of {count} x 3 x 3 is needed")
+            if not x.is_cuda or x.device.index != self.device:
+                raise ValueError("update_mesh_device: the tensor is not on the scene's device")
+            return x.data_ptr()
+        root = abi.BvhNode()
+        pt, pn = ptr(d_triangles), ptr(d_normals)
+        _check(lib().rt_scene_update_mesh_device(self._h, mesh_index, C.c_void_p(pt) if pt else None,
+                                                 C.c_void_p(pn) if pn else None, C.byref(root)))
+        return root
+
+    def mesh_table(self, mesh_index, which):
+        """rt_debug_scene_mesh_table: one mesh's slice of a scene table (abi.RT_MESH_TABLE_*) as a uint8 array."""
+        size = C.c_size_t()
+        _check(lib().rt_debug_scene_mesh_table(self._h, mesh_index, which, None, 0, C.byref(size)))
+        out = np.zeros(size.value, np.uint8)
+        _check(lib().rt_debug_scene_mesh_table(self._h, mesh_index, which, out.ctypes.data_as(C.c_void_p), out.size,
+                                               C.byref(size)))
+        return out
 
     def primitive_transforms(self):
         """rt_scene_primitive_transforms: the resolved transform of every primitive as of the upload or the last

@@ -32,6 +32,8 @@ RT_SHADOW_LAUNCH_AUTO, RT_SHADOW_LAUNCH_SEPARATE, RT_SHADOW_LAUNCH_MERGED = rang
  RT_INTEGRATOR_GROUND_TRUTH_ITERATIVE, RT_INTEGRATOR_NORMALS, RT_INTEGRATOR_DISTANCES) = range(6)
 RT_INTEGRATOR_COUNT = 6
 RT_RNG_PER_SAMPLE, RT_RNG_TILE_STREAM = 0, 1
+(RT_MESH_TABLE_TRIANGLES, RT_MESH_TABLE_NORMALS, RT_MESH_TABLE_NODES_SRC, RT_MESH_TABLE_NODES, RT_MESH_TABLE_NODES4,
+ RT_MESH_TABLE_MID4, RT_MESH_TABLE_BVH4_SOURCES, RT_MESH_TABLE_REFIT_PLAN, RT_MESH_TABLE_COUNT) = range(9)   # rt_mesh_table
 RT_HIT_MISS = 0xFFFFFFFF
 RT_HIT_PLANE_BIT = 0x80000000
 RTH_BVH_MIDPOINT_SPLIT, RTH_BVH_SAH_BINNED, RTH_BVH_SAH_FULL = range(3)
@@ -422,6 +424,9 @@ ABI_FUNCTIONS = {
                                               P(C.c_float), P(C.c_float), P(C.c_float), P(Stats)]),
     "rt_scene_update_instances": (C.c_int, [C.c_void_p, P(SceneDesc)]),
     "rt_scene_primitive_transforms": (C.c_int, [C.c_void_p, C.c_uint32, P(M4x4Inv), P(C.c_uint32)]),
+    "rt_scene_update_mesh_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, P(BvhNode)]),
+    "rt_scene_update_mesh": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_float), P(C.c_float), P(BvhNode)]),
+    "rt_debug_scene_mesh_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, P(C.c_size_t)]),
     "rt_motion_table": (C.c_int, [C.c_uint32, P(M4x4Inv), P(M4x4Inv), P(MotionEntry)]),
     "rt_temporal_accumulate_motion_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        P(Camera), C.c_float, C.c_uint32, C.c_uint32, P(TemporalParams),
@@ -463,6 +468,7 @@ HOST_FUNCTIONS = {
     "rth_set_environment_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(V3)]),
     "rth_create_scene_bvh": (C.c_int, [C.c_void_p]),
     "rth_set_primitive_transform": (C.c_int, [C.c_void_p, C.c_uint32, P(M4x4Inv)]),
+    "rth_update_mesh": (C.c_int, [C.c_void_p, C.c_uint32, P(V3), P(V3)]),
     "rth_set_bvh_device": (None, [C.c_int]),
     "rth_build_bvh_entries": (C.c_int, [C.c_uint32, P(V3), P(V3), C.c_int32, P(BvhNode), P(C.c_uint32), P(C.c_uint32)]),
     "rth_scene_desc": (P(SceneDesc), [C.c_void_p]),

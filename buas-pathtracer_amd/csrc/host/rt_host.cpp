@@ -874,6 +874,89 @@ int rth_set_primitive_transform(rth_scene* s, uint32_t primitive_id, const rt_m4
     return 1;
 }
 
+}  // extern "C"
+
+// The refit of DESIGN.md ("Deforming meshes").  min and max in the total order that puts -0 below +0, so a fold's
+// result does not depend on its order; a pair (lo, hi) starts empty at (+inf, -inf).
+namespace {
+inline float tmin(float a, float b) { return (a < b || (a == b && std::signbit(a))) ? a : b; }
+inline float tmax(float a, float b) { return (a > b || (a == b && !std::signbit(a))) ? a : b; }
+struct Pair { float lo[3], hi[3]; };
+inline Pair empty_pair() {
+    const float inf = std::numeric_limits<float>::infinity();
+    return {{inf, inf, inf}, {-inf, -inf, -inf}};
+}
+inline void join(Pair& a, const Pair& b) {
+    for (int k = 0; k < 3; ++k) { a.lo[k] = tmin(a.lo[k], b.lo[k]); a.hi[k] = tmax(a.hi[k], b.hi[k]); }
+}
+// a triangle's centre and half extent per axis; false when box_within's expression fails on them
+inline bool triangle_box(const rt_v3* v, float p[3], float r[3]) {
+    const float a[3] = {v[0].x, v[0].y, v[0].z}, b[3] = {v[1].x, v[1].y, v[1].z}, c[3] = {v[2].x, v[2].y, v[2].z};
+    bool ok = true;
+    for (int k = 0; k < 3; ++k) {
+        const float lo = tmin(a[k], tmin(b[k], c[k])), hi = tmax(a[k], tmax(b[k], c[k]));
+        p[k] = 0.5f*(lo + hi);
+        r[k] = 0.5f*(hi - lo);
+        ok = ok && std::isfinite(a[k]) && std::isfinite(b[k]) && std::isfinite(c[k]) &&
+             std::fabs(p[k]) + std::fabs(r[k]) <= 1099511627776.0f;
+    }
+    return ok;
+}
+// node i's pair from the slots' extents; writes the box of every node that has a triangle below it
+bool refit_node(std::vector<rt_bvh_node>& nodes, const std::vector<Pair>& ext, uint32_t i, std::vector<uint8_t>& seen, Pair& out) {
+    if (seen[i]) return false;
+    seen[i] = 1;
+    rt_bvh_node& n = nodes[i];
+    out = empty_pair();
+    if (n.count) {
+        for (uint32_t t = n.left_first; t < n.left_first + n.count; ++t) join(out, ext[t]);
+    } else if (n.left_first != 0 && (size_t)n.left_first + 1 < nodes.size()) {
+        Pair l, r;
+        if (!refit_node(nodes, ext, n.left_first, seen, l) || !refit_node(nodes, ext, n.left_first + 1, seen, r)) return false;
+        join(out, l);
+        join(out, r);
+    }
+    if (out.lo[0] <= out.hi[0]) {
+        n.bv_p = {0.5f*(out.lo[0] + out.hi[0]), 0.5f*(out.lo[1] + out.hi[1]), 0.5f*(out.lo[2] + out.hi[2])};
+        n.bv_r = {0.5f*(out.hi[0] - out.lo[0]), 0.5f*(out.hi[1] - out.lo[1]), 0.5f*(out.hi[2] - out.lo[2])};
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
+int rth_update_mesh(rth_scene* s, uint32_t mesh_id, const rt_v3* triangles, const rt_v3* normals) {
+    if (!s) { set_err("rth_update_mesh: null scene"); return 0; }
+    if (mesh_id >= s->meshes.size()) { set_err("rth_update_mesh: mesh id out of range"); return 0; }
+    Mesh& m = s->meshes[mesh_id];
+    const size_t n = m.indices.size();
+    if (n && !triangles) { set_err("rth_update_mesh: null triangles"); return 0; }
+    if (normals && !m.has_normals) { set_err("rth_update_mesh: normals for a mesh created without normals"); return 0; }
+    std::vector<Pair> ext(n);
+    for (size_t t = 0; t < n; ++t) {
+        float p[3], r[3];
+        if (!triangle_box(triangles + 3*(size_t)m.indices[t], p, r)) {
+            set_err("rth_update_mesh: a vertex is not finite or a triangle's box is not within 2^40 of the origin");
+            return 0;
+        }
+        for (int k = 0; k < 3; ++k) { ext[t].lo[k] = p[k] - r[k]; ext[t].hi[k] = p[k] + r[k]; }
+    }
+    for (const rt_bvh_node& nd : m.nodes)
+        if (nd.count && (size_t)nd.left_first + nd.count > n) { set_err("rth_update_mesh: mesh BVH node out of range"); return 0; }
+    if (!m.nodes.empty()) {
+        std::vector<rt_bvh_node> nodes = m.nodes;
+        std::vector<uint8_t> seen(nodes.size(), 0);
+        Pair root;
+        if (!refit_node(nodes, ext, 0u, seen, root)) { set_err("rth_update_mesh: the mesh BVH is not a tree"); return 0; }
+        m.nodes.swap(nodes);
+    }
+    for (size_t t = 0; t < n; ++t)
+        for (int k = 0; k < 3; ++k) m.tris[3*t + k] = triangles[3*(size_t)m.indices[t] + k];
+    if (normals) m.normals.assign(normals, normals + 3*n);
+    return 1;
+}
+
 const rt_scene_desc* rth_scene_desc(rth_scene* s) {
     s->mesh_descs.resize(s->meshes.size());
     for (size_t i = 0; i < s->meshes.size(); ++i) {

@@ -4071,10 +4071,28 @@ struct rt_scene {
         std::vector<rt_m4x4inv> resolved;       // per primitive: transforms[transform_index] (rt_scene_primitive_transforms)
         static constexpr int TABLES = 9;        // install_instance_tables' tables
         size_t table_bytes[TABLES] = {};        // and the bytes each one's allocation holds
+        std::vector<uint32_t> mesh_tris;        // per mesh: triangle_count
+        std::vector<uint32_t> mesh4;            // per mesh: the BVH4 nodes before its own (mesh_count + 1 entries)
+        std::vector<uint8_t> within_each;       // per mesh: mesh_within's term, from the first rt_scene_update_mesh on
     } keep;
+    // rt_scene_update_mesh (rt_refit.hip): the mesh whose root box no longer matches the instance tables and the
+    // top-level BVH (-1: none; rt_scene_update_instances clears it), and that file's per-scene state with its destructor
+    long long stale_mesh = -1;
+    void* refit = nullptr;
+    void (*refit_free)(void*) = nullptr;
 };
 
 namespace {
+
+// Every entry that traces rays through the scene passes here first (run_frame, rt_gbuffer_device,
+// rt_debug_intersect): after rt_scene_update_mesh changed a mesh's root box, the instance tables and the caller's
+// top-level BVH still hold the old one, and a walk through them would miss what left it.
+int scene_stale(const rt_scene* s, const char* what) {
+    if (s->stale_mesh < 0) return RT_OK;
+    set_error(std::string(what) + ": the bounds of mesh " + std::to_string(s->stale_mesh) + " changed in rt_scene_update_mesh: "
+              "call rt_scene_update_instances with a top-level BVH over the new bounds first");
+    return RT_ERROR_INVALID;
+}
 
 template <typename T>
 int upload(rt_scene* s, const T* host, size_t count, const T** out) {
@@ -4148,7 +4166,8 @@ std::vector<float4> top_sequences(const rt_bvh_node* nodes, uint32_t count, uint
 // src (optional): the BVH2 node each BVH4 node was built from, by BVH4 index (mid4's boxes).
 // levels: the BVH4 levels below and including this node (a reference-unit walk's markers, need_ref).
 uint32_t build_bvh4(const rt_bvh_node* n, uint32_t count, uint32_t i, std::vector<float4>& out,
-                    uint32_t& need, bool& ok, std::vector<uint32_t>* src = nullptr, uint32_t* levels = nullptr) {
+                    uint32_t& need, bool& ok, std::vector<uint32_t>* src = nullptr, uint32_t* levels = nullptr,
+                    std::vector<uint32_t>* slots = nullptr) {
     const uint32_t k = (uint32_t)(out.size() / 8);
     out.resize(out.size() + 8, make_float4(0, 0, 0, 0));
     if (src) { src->resize(k + 1); (*src)[k] = i; }
@@ -4166,6 +4185,7 @@ uint32_t build_bvh4(const rt_bvh_node* n, uint32_t count, uint32_t i, std::vecto
             }
         }
     }
+    if (slots) { slots->resize(4*(size_t)k + 4); for (int j = 0; j < 4; ++j) (*slots)[4*(size_t)k + j] = slot[j]; }
     float4 q[8];
     for (int j = 0; j < 8; ++j) q[j] = make_float4(0, 0, 0, 0);
     uint32_t nchild = 0, deeper = 0, lv = 0;
@@ -4179,7 +4199,7 @@ uint32_t build_bvh4(const rt_bvh_node* n, uint32_t count, uint32_t i, std::vecto
             ++nchild;
             if (interior(m)) {
                 uint32_t cn = 0, cl = 0;
-                rec = build_bvh4(n, count, m, out, cn, ok, src, &cl);
+                rec = build_bvh4(n, count, m, out, cn, ok, src, &cl, slots);
                 deeper = std::max(deeper, cn);
                 lv = std::max(lv, cl);
             } else {
@@ -4441,6 +4461,7 @@ void launch_resolve_tiles(const SplatCfg& sp, const FrameParams& fp, const Pool&
 // bookkeep of every chunk's last iteration), and the buffers are added at the end.
 int run_frame(rt_scene* s, const rt_settings* st, FrameParams fp, unsigned long long total, hipStream_t stream,
               const SplatCfg& sp, rt_stats* stats, bool shard) {
+    if (int stale = scene_stale(s, "a frame")) return stale;
     auto t0 = std::chrono::steady_clock::now();
     // st: device_settings() of the caller's.  The integrators besides the Advanced one have no NEE: they
     // queue no shadow ray, so no connect launch is made (the frame runs the separate schedule without it),
@@ -5508,6 +5529,9 @@ int rt_scene_upload(const rt_scene_desc* d, int device, rt_scene** out) {
             k.mesh_nodes[m] = d->meshes[m].node_count;
             if (d->meshes[m].node_count) k.mesh_root[m] = d->meshes[m].nodes[0];
         }
+        k.mesh_tris.assign(d->mesh_count, 0u);
+        for (uint32_t m = 0; m < d->mesh_count; ++m) k.mesh_tris[m] = d->meshes[m].triangle_count;
+        k.mesh4 = mesh4;
         k.mesh_depth = mesh_depth; k.mesh_depth_ref = mesh_depth_ref;
         k.mesh_within = true;
         for (size_t i = 0; i < mnodes.size() && k.mesh_within; ++i) k.mesh_within = box_within(mnodes[i]);
@@ -5679,7 +5703,9 @@ int rt_scene_update_instances(rt_scene* s, const rt_scene_desc* d) {
     // the device from here on: no frame of the scene may still read a table that goes
     if ((err = bind_device(s->device))) return err;
     HIP_OK(hipDeviceSynchronize());
-    return install_instance_tables(s, d, it);
+    err = install_instance_tables(s, d, it);
+    if (!err) s->stale_mesh = -1;           // the tables now hold every mesh's root box as it is
+    return err;
 }
 
 int rt_scene_primitive_transforms(const rt_scene* s, uint32_t cap, rt_m4x4inv* out, uint32_t* out_count) {
@@ -5709,6 +5735,7 @@ int rt_scene_free(rt_scene* s) {
     if (s->d_aux) (void)hipFree(s->d_aux);
     if (s->frames) (void)hipFree(s->frames);
     if (s->gbuf_spill) (void)hipFree(s->gbuf_spill);
+    if (s->refit && s->refit_free) s->refit_free(s->refit);
     delete s;
     return RT_OK;
 }
@@ -6504,6 +6531,7 @@ int rt_debug_verify_div3(int device, uint32_t count, const float* sets, uint64_t
 
 int rt_debug_intersect(rt_scene* s, uint32_t count, const rt_ray_query* rays, int occlusion, rt_hit_record* out) {
     if (!s || !rays || !out) { set_error("null argument"); return RT_ERROR_INVALID; }
+    if (int stale = scene_stale(s, "rt_debug_intersect")) return stale;
     if (!count) return RT_OK;
     HIP_OK(hipSetDevice(s->device));
     rt_ray_query* d_r = nullptr; rt_hit_record* d_o = nullptr;
@@ -6541,6 +6569,7 @@ int rt_gbuffer_device(rt_scene* s, const rt_camera* c, float lens_distortion, ui
                       rt_gbuffer_texel* d_out, void* hip_stream) {
     int err = check_gbuffer("rt_gbuffer_device", s, c, w, h, d_out, "d_out");
     if (err) return err;
+    if ((err = scene_stale(s, "rt_gbuffer_device"))) return err;
     err = bind_device(s->device);
     if (err) return err;
     // the spill area of the largest grid, once per scene (rt_scene_free frees it)
@@ -6586,3 +6615,66 @@ void rt_internal_set_error(const char* message) { set_error(message); }
 int rt_internal_bind_device(int device) { return bind_device(device); }
 int rt_internal_scene_device(const rt_scene* scene) { return scene->device; }
 int rt_internal_scene_cancelled(const rt_scene* scene) { return scene->cancel; }
+
+uint32_t rt_internal_scene_mesh_count(const rt_scene* scene) { return (uint32_t)scene->keep.meshes.size(); }
+void rt_internal_scene_mesh(rt_scene* scene, uint32_t m, RtMeshSlices* out) {
+    const rt_scene::Keep& k = scene->keep;
+    const DevScene& ds = scene->ds;
+    const DevMesh& dm = k.meshes[m];
+    RtMeshSlices o = {};
+    o.tri_count = k.mesh_tris[m];
+    o.node_count = k.mesh_nodes[m];
+    o.n4_first = k.mesh4[m];
+    o.n4_count = k.mesh4[m + 1] - k.mesh4[m];
+    o.has_normals = dm.has_normals;
+    // the tables are const to the render kernels, not to the scene that owns them
+    if (o.tri_count) {
+        o.tris = const_cast<float*>(reinterpret_cast<const float*>(ds.tris)) + 12*(size_t)dm.tri_offset;
+        o.tri_orig = ds.tri_orig + dm.tri_offset;
+        o.normals = const_cast<float*>(ds.normals) + 9*(size_t)dm.tri_offset;
+    }
+    if (o.node_count) {
+        o.nodes_src = const_cast<rt_bvh_node*>(ds.mnodes_src) + dm.node_offset;
+        o.nodes = const_cast<rt_bvh_node*>(ds.mnodes) + dm.node_offset;
+    }
+    if (o.n4_count) {
+        o.nodes4 = const_cast<float*>(reinterpret_cast<const float*>(ds.mnodes4)) + 32*(size_t)o.n4_first;
+        o.mid4 = const_cast<float*>(reinterpret_cast<const float*>(ds.mid4)) + 12*(size_t)o.n4_first;
+    }
+    *out = o;
+}
+void rt_internal_mesh_bvh4_plan(const rt_bvh_node* nodes, uint32_t count, std::vector<uint32_t>& src, std::vector<uint32_t>& slots) {
+    src.clear(); slots.clear();
+    if (!count || nodes[0].count) return;           // a root that is a leaf has no BVH4 node (rt_scene_upload)
+    std::vector<float4> q;
+    bool ok = true;
+    uint32_t need = 0, levels = 0;
+    (void)build_bvh4(nodes, count, 0u, q, need, ok, &src, &levels, &slots);
+}
+void** rt_internal_scene_refit_state(rt_scene* scene, void (*free_state)(void*)) {
+    scene->refit_free = free_state;
+    return &scene->refit;
+}
+int rt_internal_scene_mesh_refitted(rt_scene* scene, uint32_t m, const float* box, bool within, rt_bvh_node* out_root) {
+    rt_scene::Keep& k = scene->keep;
+    if (k.within_each.empty()) {
+        k.within_each.assign(k.meshes.size(), 1);
+        if (!k.mesh_within) {                       // which meshes: from the device's copy, once per scene
+            for (size_t i = 0; i < k.meshes.size(); ++i) {
+                std::vector<rt_bvh_node> n(k.mesh_nodes[i]);
+                if (!n.empty())
+                    HIP_OK(hipMemcpy(n.data(), scene->ds.mnodes_src + k.meshes[i].node_offset, sizeof(rt_bvh_node)*n.size(), hipMemcpyDeviceToHost));
+                for (const rt_bvh_node& nd : n) if (!box_within(nd)) k.within_each[i] = 0;
+            }
+        }
+    }
+    k.within_each[m] = within ? 1 : 0;
+    k.mesh_within = true;
+    for (uint8_t w : k.within_each) k.mesh_within = k.mesh_within && w;
+    if (box && memcmp(&k.mesh_root[m].bv_p, box, 24) != 0) {
+        memcpy(&k.mesh_root[m].bv_p, box, 24);
+        scene->stale_mesh = m;
+    }
+    if (out_root) *out_root = k.mesh_root[m];
+    return RT_OK;
+}

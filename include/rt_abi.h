@@ -1058,6 +1058,51 @@ int rt_render_temporal_motion(rt_scene* scene, const rt_camera* camera, const rt
                               rt_temporal_motion_state* state, float* out_pixels, float* out_length,
                               rt_stats* stats);
 
+/* Deforming meshes after upload (beyond the reference, an opt-in: new entries only, no other entry's behaviour
+ * changes; RT_ABI_VERSION stays).  DESIGN.md ("Deforming meshes") defines the refit operation by operation; the
+ * kernels match tests/ref_refit/ref_refit.c and rth_update_mesh byte for byte.
+ *
+ * rt_scene_update_mesh_device gives mesh `mesh_index` of an uploaded scene new vertices.  d_triangles (on the scene's
+ * device) holds 9 floats per triangle, a b c, in the ORIGINAL order: the order rth_create_mesh took them in, which
+ * is rt_mesh::normals' order and what rt_mesh::indices maps a BVH slot to.  d_normals holds 3 x 3 floats per triangle
+ * in the same order, or is NULL: the stored normals stay.  The mesh's topology stays: left_first, count, split_axis,
+ * the slot order and the BVH4's records.  Rewritten, for this mesh only: its triangle records, its slot-order
+ * normals, the box of every node reachable from node 0 that has a triangle below it (in both node tables), the
+ * child boxes of its BVH4 nodes and their skipped-level boxes.  out_root (optional) receives node 0 afterwards.
+ * Refused with RT_ERROR_INVALID, by name, before any table changes: a null scene, a mesh_index out of range, null
+ * triangles for a mesh that has some, normals for a mesh uploaded without, a vertex that is not finite or a triangle
+ * whose box is not within 2^40 of the origin (a reduction on the device; its flag comes back in one small copy), a
+ * mesh BVH that is no tree.  A refused call leaves every table's bytes as they were.  The entry synchronises the
+ * device first and is complete on return.
+ * When node 0's box changed, the scene is stale: its instance tables and the caller's top-level BVH still hold the
+ * old box.  Until a successful rt_scene_update_instances (with a top-level BVH over the new bounds) every entry that
+ * traces rays through the scene returns RT_ERROR_INVALID and says so.  An update that leaves the root box's bytes as
+ * they were does not make the scene stale.  After update + rt_scene_update_instances every entry on the scene is
+ * bit-identical to the same entry on a fresh rt_scene_upload of the rth_update_mesh-ed host scene. */
+int rt_scene_update_mesh_device(rt_scene* scene, uint32_t mesh_index, const float* d_triangles, const float* d_normals,
+                                rt_bvh_node* out_root);
+/* Same, with triangles and normals in host memory. */
+int rt_scene_update_mesh(rt_scene* scene, uint32_t mesh_index, const float* triangles, const float* normals,
+                         rt_bvh_node* out_root);
+/* For the tests: one mesh's slice of a scene table, copied to `out` (cap bytes); *out_bytes = the slice's size.  out
+ * NULL asks for the size alone; a cap below it is RT_ERROR_INVALID.  The two plan tables build the mesh's refit plan
+ * when no update has yet. */
+enum rt_mesh_table {
+    RT_MESH_TABLE_TRIANGLES    = 0,   /* 12 floats per slot: (a, 0), (b - a, 0), (c - a, 0)                  */
+    RT_MESH_TABLE_NORMALS      = 1,   /* 9 floats per slot                                                   */
+    RT_MESH_TABLE_NODES_SRC    = 2,   /* rt_bvh_node per node, the caller's layout                           */
+    RT_MESH_TABLE_NODES        = 3,   /* the traversal layout: the same boxes, the packed record, 0          */
+    RT_MESH_TABLE_NODES4       = 4,   /* 32 floats per BVH4 node (rt_debug_mesh_bvh4's layout)               */
+    RT_MESH_TABLE_MID4         = 5,   /* 12 floats per BVH4 node: pL rL pR rR of its BVH2 node's children    */
+    RT_MESH_TABLE_BVH4_SOURCES = 6,   /* uint32 per BVH4 node: the BVH2 node it was made from                */
+    /* 8 uint32: launches of the subtree kernel (rounds), subtrees, subtrees of the first round, nodes reachable from
+     * node 0, the largest subtree's nodes, the most levels in one subtree, BVH4 nodes, kernel launches per update */
+    RT_MESH_TABLE_REFIT_PLAN   = 7,
+    RT_MESH_TABLE_COUNT        = 8
+};
+int rt_debug_scene_mesh_table(const rt_scene* scene, uint32_t mesh_index, int which, void* out, size_t cap,
+                              size_t* out_bytes);
+
 /* The reference's top-down BVH builders on the device (RT/bvh.cpp:222-326 with
  * partition_midpoint :53-61, partition_sah_binned :138-213 or the full SAH sweep
  * partition_objects_sah / evaluate_sah :63-131, the partition of :26-51): one launch per

@@ -109,6 +109,15 @@ int      rth_create_scene_bvh(rth_scene* s);
  * slot of its own.  The top-level BVH is stale until rth_create_scene_bvh is called again; rth_scene_desc then
  * returns the new desc (for rt_scene_update_instances or a fresh rt_scene_upload).  Returns 0 on a bad id. */
 int      rth_set_primitive_transform(rth_scene* s, uint32_t primitive_id, const rt_m4x4inv* transform);
+/* Deform a mesh (beyond the reference): mesh `mesh_id` gets new vertices, `triangles` holding 3 per triangle in the
+ * order rth_create_mesh took them in, and its BVH is refitted by DESIGN.md's definition ("Deforming meshes"): the
+ * topology, `indices` and every node's left_first, count and split_axis stay, every node reachable from node 0 that
+ * has a triangle below it gets the box the builder gives that topology.  `normals` (the same order) replaces the
+ * stored normals; NULL keeps them, and normals for a mesh created without are refused.  A non-finite vertex or a
+ * triangle whose box leaves 2^40 is refused.  A refused call changes nothing and returns 0 (rth_last_error says
+ * why).  The top-level BVH is stale until rth_create_scene_bvh is called again, as after
+ * rth_set_primitive_transform; rt_scene_update_mesh is the same operation on an uploaded scene. */
+int      rth_update_mesh(rth_scene* s, uint32_t mesh_id, const rt_v3* triangles, const rt_v3* normals);
 /* Flattened view, valid until the scene is modified or destroyed. */
 const rt_scene_desc* rth_scene_desc(rth_scene* s);
 
