@@ -24,7 +24,8 @@ from . import abi
 from .abi import (V3, v3, M4x4Inv, Material, Camera, Settings, FilterCache, PostSettings, TileSet, Stats,
                   AccumulationBuffer, RayQuery, HitRecord, BvhInfo, DenoiseParams, DenoiseFeaturesParams,
                   TileErrorParams, AdaptiveParams, RobustParams, GBufferTexel, TemporalParams, TemporalState,
-                  DenoiseVarianceParams, TemporalFilteredState, MotionEntry, TemporalMotionState)
+                  DenoiseVarianceParams, TemporalFilteredState, MotionEntry, TemporalMotionState, SurfaceTexel,
+                  DeformMesh, DeformEntry)
 
 __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settings", "load_reconstruction_kernel",
            "translate", "scale", "rotate_x", "rotate_y", "rotate_z", "identity", "aim_camera", "aim_camera_at",
@@ -40,7 +41,9 @@ __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settin
            "denoise_variance_workspace_bytes", "temporal_filtered_workspace_bytes", "temporal_accumulate_moments",
            "temporal_accumulate_moments_device", "temporal_variance", "temporal_variance_device", "denoise_variance",
            "denoise_variance_device", "MotionEntry", "TemporalMotionState", "motion_table", "temporal_accumulate_motion",
-           "temporal_accumulate_motion_device", "temporal_motion_workspace_bytes"]
+           "temporal_accumulate_motion_device", "temporal_motion_workspace_bytes", "SurfaceTexel", "DeformMesh",
+           "DeformEntry", "deform_meshes", "temporal_deform_workspace_bytes", "temporal_accumulate_deform",
+           "temporal_accumulate_deform_device"]
 
 PI_32 = 3.14159265359
 DEG_TO_RAD = 6.28318530717 / 360.0
@@ -718,6 +721,71 @@ class DeviceScene:
                                                       C.c_void_p(stream) if stream else None, C.byref(stats)))
         return stats
 
+    def gbuffer_surface(self, camera, w, h, lens_distortion=0.0):
+        """rt_gbuffer_surface: gbuffer() and, beside it, a structured array (h, w) of abi.SURFACE_DTYPE {triangle, v, w,
+        reserved}: the mesh-local original triangle index and the barycentrics of a hit on a mesh, {0xFFFFFFFF, 0, 0, 0}
+        elsewhere -> (gbuffer, surface)."""
+        out = np.zeros((h, w), abi.GBUFFER_DTYPE)
+        surface = np.zeros((h, w), abi.SURFACE_DTYPE)
+        _check(lib().rt_gbuffer_surface(self._h, C.byref(camera), float(lens_distortion), w, h,
+                                        out.ctypes.data_as(C.POINTER(GBufferTexel)),
+                                        surface.ctypes.data_as(C.POINTER(SurfaceTexel))))
+        return out, surface
+
+    def gbuffer_surface_device(self, camera, w, h, d_out, d_surface, lens_distortion=0.0, stream=None):
+        """rt_gbuffer_surface_device into device pointers of w*h 32-byte texels and w*h 16-byte surface records."""
+        _check(lib().rt_gbuffer_surface_device(self._h, C.byref(camera), float(lens_distortion), w, h, C.c_void_p(d_out),
+                                               C.c_void_p(d_surface) if d_surface else None,
+                                               C.c_void_p(stream) if stream else None))
+
+    def deform_table(self, meshes, prev):
+        """rt_scene_deform_table (no device work): `meshes` a list of (mesh_index, d_prev_triangles, d_prev_normals or
+        None) with device pointers or torch tensors (or a DeformMesh array), `prev` the transforms primitive_transforms()
+        returned the frame before -> a structured array of abi.DEFORM_DTYPE."""
+        prev = np.ascontiguousarray(prev, abi.M4X4INV_DTYPE)
+        arr = deform_meshes(meshes)
+        out = np.zeros(prev.shape[0], abi.DEFORM_DTYPE)
+        _check(lib().rt_scene_deform_table(self._h, len(arr), arr if len(arr) else None, prev.shape[0],
+                                           prev.ctypes.data_as(C.POINTER(M4x4Inv)),
+                                           out.ctypes.data_as(C.POINTER(DeformEntry))))
+        return out
+
+    def render_temporal_deform(self, camera, settings, filter_cache, w, h, state, meshes=(), params=None, frame_count=0,
+                               total_frame_index=0, tile=64, shard_index=0, shard_count=1, want_length=True):
+        """rt_render_temporal_deform: render_temporal_motion with a history that also follows update_mesh.  `state` is a
+        TemporalMotionState whose d_workspace points at temporal_deform_workspace_bytes(w, h, primitive count) bytes;
+        `meshes` lists what was deformed since the previous frame as deform_table() takes it, each with the vertex
+        buffer the previous frame was rendered with -> (history, length or None, the beauty frame's stats)."""
+        if params is None:
+            params = default_temporal_params()
+        out = np.zeros((h, w, 4), np.float32)
+        length = np.zeros((h, w), np.float32) if want_length else None
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        arr = deform_meshes(meshes)
+        fp = C.POINTER(C.c_float)
+        _check(lib().rt_render_temporal_deform(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                               C.byref(tiles), total_frame_index, w, h, frame_count, C.byref(params),
+                                               C.byref(state), len(arr), arr if len(arr) else None, out.ctypes.data_as(fp),
+                                               length.ctypes.data_as(fp) if want_length else None, C.byref(stats)))
+        return out, length, stats
+
+    def render_temporal_deform_device(self, camera, settings, filter_cache, w, h, params, state, meshes, d_out,
+                                      d_length_out=None, stream=None, frame_count=0, total_frame_index=0, tile=64,
+                                      shard_index=0, shard_count=1):
+        """rt_render_temporal_deform_device into device pointers (as render_temporal_motion_device); `state` and
+        `meshes` as for render_temporal_deform -> the beauty frame's stats."""
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        arr = deform_meshes(meshes)
+        _check(lib().rt_render_temporal_deform_device(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                                      C.byref(tiles), total_frame_index, w, h, frame_count,
+                                                      C.byref(params), C.byref(state), len(arr),
+                                                      arr if len(arr) else None, C.c_void_p(d_out),
+                                                      C.c_void_p(d_length_out) if d_length_out else None,
+                                                      C.c_void_p(stream) if stream else None, C.byref(stats)))
+        return stats
+
     def render_temporal_filtered(self, camera, settings, filter_cache, w, h, state, params=None, filter_params=None,
                                  spatial_below=abi.RT_TEMPORAL_SPATIAL_BELOW_DEFAULT, frame_count=0, total_frame_index=0,
                                  tile=64, shard_index=0, shard_count=1, want_extras=True):
@@ -1076,6 +1144,87 @@ def temporal_accumulate_motion_device(d_current, d_gbuffer, d_prev_history, d_pr
                                                       float(prev_lens_distortion), w, h, C.byref(params), vp(d_history),
                                                       vp(d_length), vp(stream), vp(d_motion), motion_count,
                                                       vp(d_prev_moments), vp(d_moments), vp(d_velocity)))
+
+
+def deform_meshes(meshes):
+    """A list of (mesh_index, d_prev_triangles, d_prev_normals or None), pointers or torch tensors -> a DeformMesh
+    array (the tensors must stay alive while it is used); a DeformMesh array passes through."""
+    if isinstance(meshes, C.Array):
+        return meshes
+    ptr = lambda x: None if x is None else (x if isinstance(x, int) else x.data_ptr())
+    arr = (DeformMesh*len(meshes))()
+    for k, (m, t, n) in enumerate(meshes):
+        arr[k] = DeformMesh(m, 0, ptr(t), ptr(n))
+    return arr
+
+
+def temporal_deform_workspace_bytes(w, h, primitive_count):
+    """rt_temporal_deform_workspace_bytes (no device needed): temporal_motion_workspace_bytes, the surface records and
+    the deform table."""
+    return int(lib().rt_temporal_deform_workspace_bytes(w, h, primitive_count))
+
+
+def temporal_accumulate_deform(current, gbuffer, prev=None, prev_camera=None, prev_lens_distortion=0.0, params=None,
+                               motion=None, surface=None, deform=None, want_moments=False, want_velocity=False, device=0):
+    """The deform-aware accumulate stage on the GPU (rt_temporal_accumulate_deform): temporal_accumulate_motion's
+    arguments, `surface` (h, w) of abi.SURFACE_DTYPE and `deform` a table of abi.DEFORM_DTYPE (its vertex pointers
+    device pointers) or None -> (history, length, moments or None, velocity or None)."""
+    current = np.ascontiguousarray(current, np.float32)
+    h, w, _ = current.shape
+    gbuffer = np.ascontiguousarray(gbuffer, abi.GBUFFER_DTYPE)
+    assert gbuffer.shape == (h, w)
+    if params is None:
+        params = default_temporal_params()
+    fp, gp = C.POINTER(C.c_float), C.POINTER(GBufferTexel)
+    ph = pl = pg = pm = None
+    if prev is not None:
+        ph = np.ascontiguousarray(prev[0], np.float32)
+        pl = np.ascontiguousarray(prev[1], np.float32)
+        pg = np.ascontiguousarray(prev[2], abi.GBUFFER_DTYPE)
+        assert ph.shape == (h, w, 4) and pl.shape == (h, w) and pg.shape == (h, w)
+        if want_moments:
+            pm = np.ascontiguousarray(prev[3], np.float32)
+            assert pm.shape == (h, w, 2)
+    count = dcount = 0
+    if motion is not None:
+        motion = np.ascontiguousarray(motion, abi.MOTION_DTYPE)
+        count = motion.shape[0]
+    if deform is not None:
+        deform = np.ascontiguousarray(deform, abi.DEFORM_DTYPE)
+        dcount = deform.shape[0]
+    if surface is not None:
+        surface = np.ascontiguousarray(surface, abi.SURFACE_DTYPE)
+        assert surface.shape == (h, w)
+    history = np.zeros((h, w, 4), np.float32)
+    length = np.zeros((h, w), np.float32)
+    moments = np.zeros((h, w, 2), np.float32) if want_moments else None
+    velocity = np.zeros((h, w, 2), np.float32) if want_velocity else None
+    opt = lambda a, t: None if a is None else a.ctypes.data_as(t)
+    _check(lib().rt_temporal_accumulate_deform(device, current.ctypes.data_as(fp), gbuffer.ctypes.data_as(gp), opt(ph, fp),
+                                               opt(pl, fp), opt(pg, gp),
+                                               None if prev_camera is None else C.byref(prev_camera),
+                                               float(prev_lens_distortion), w, h, C.byref(params),
+                                               history.ctypes.data_as(fp), length.ctypes.data_as(fp),
+                                               opt(motion if count else None, C.POINTER(MotionEntry)), count, opt(pm, fp),
+                                               opt(moments, fp), opt(velocity, fp), opt(surface, C.POINTER(SurfaceTexel)),
+                                               opt(deform if dcount else None, C.POINTER(DeformEntry)), dcount))
+    return history, length, moments, velocity
+
+
+def temporal_accumulate_deform_device(d_current, d_gbuffer, d_prev_history, d_prev_length, d_prev_gbuffer, prev_camera,
+                                      prev_lens_distortion, w, h, params, d_history, d_length, d_motion=None, motion_count=0,
+                                      d_prev_moments=None, d_moments=None, d_velocity=None, d_surface=None, d_deform=None,
+                                      deform_count=0, device=0, stream=None):
+    """rt_temporal_accumulate_deform_device on device pointers: temporal_accumulate_motion_device's arguments, the
+    surface records and the deform table."""
+    vp = lambda a: C.c_void_p(a) if a else None
+    _check(lib().rt_temporal_accumulate_deform_device(device, vp(d_current), vp(d_gbuffer), vp(d_prev_history),
+                                                      vp(d_prev_length), vp(d_prev_gbuffer),
+                                                      None if prev_camera is None else C.byref(prev_camera),
+                                                      float(prev_lens_distortion), w, h, C.byref(params), vp(d_history),
+                                                      vp(d_length), vp(stream), vp(d_motion), motion_count,
+                                                      vp(d_prev_moments), vp(d_moments), vp(d_velocity), vp(d_surface),
+                                                      vp(d_deform), deform_count))
 
 
 def default_denoise_variance_params():

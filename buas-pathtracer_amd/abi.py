@@ -265,6 +265,31 @@ class TemporalMotionState(C.Structure):     # rt_temporal_motion_state (moving i
                 ("transform_cap", C.c_uint32), ("d_workspace", C.c_void_p), ("transforms", C.POINTER(M4x4Inv))]
 
 
+class SurfaceTexel(C.Structure):       # rt_surface_texel (deforming meshes: where on which triangle a pixel's hit lies), 16 bytes
+    _fields_ = [("triangle", C.c_uint32), ("v", C.c_float), ("w", C.c_float), ("reserved", C.c_uint32)]
+
+
+# the numpy layout of a surface buffer: np.zeros((h, w), SURFACE_DTYPE)
+SURFACE_DTYPE = [("triangle", "<u4"), ("v", "<f4"), ("w", "<f4"), ("reserved", "<u4")]
+
+
+class DeformMesh(C.Structure):         # rt_deform_mesh (deforming meshes: one deformed mesh and last frame's vertices)
+    _fields_ = [("mesh_index", C.c_uint32), ("reserved", C.c_uint32), ("d_prev_triangles", C.c_void_p),
+                ("d_prev_normals", C.c_void_p)]
+
+
+class DeformEntry(C.Structure):        # rt_deform_entry (deforming meshes: one primitive's entry of the table), 128 bytes
+    _fields_ = [("inv_prev", (C.c_float * 4) * 3), ("fwd_prev", (C.c_float * 4) * 3), ("d_prev_triangles", C.c_void_p),
+                ("d_prev_normals", C.c_void_p), ("triangle_count", C.c_uint32), ("deformed", C.c_uint32),
+                ("has_normals", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# the numpy layout of a deform table: np.zeros(count, DEFORM_DTYPE)
+DEFORM_DTYPE = [("inv_prev", "<f4", (3, 4)), ("fwd_prev", "<f4", (3, 4)), ("d_prev_triangles", "<u8"),
+                ("d_prev_normals", "<u8"), ("triangle_count", "<u4"), ("deformed", "<u4"), ("has_normals", "<u4"),
+                ("reserved", "<u4")]
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("node_count", C.c_uint32), ("leaf_count", C.c_uint32), ("max_depth", C.c_uint32),
                 ("max_leaf_size", C.c_uint32)]
@@ -443,6 +468,29 @@ ABI_FUNCTIONS = {
     "rt_render_temporal_motion": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
                                             C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams), P(TemporalMotionState),
                                             P(C.c_float), P(C.c_float), P(Stats)]),
+    "rt_gbuffer_surface_device": (C.c_int, [C.c_void_p, P(Camera), C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "rt_gbuffer_surface": (C.c_int, [C.c_void_p, P(Camera), C.c_float, C.c_uint32, C.c_uint32, P(GBufferTexel),
+                                     P(SurfaceTexel)]),
+    "rt_scene_deform_table": (C.c_int, [C.c_void_p, C.c_uint32, P(DeformMesh), C.c_uint32, P(M4x4Inv), P(DeformEntry)]),
+    "rt_temporal_accumulate_deform_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       P(Camera), C.c_float, C.c_uint32, C.c_uint32, P(TemporalParams),
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_uint32]),
+    "rt_temporal_accumulate_deform": (C.c_int, [C.c_int, P(C.c_float), P(GBufferTexel), P(C.c_float), P(C.c_float),
+                                                P(GBufferTexel), P(Camera), C.c_float, C.c_uint32, C.c_uint32,
+                                                P(TemporalParams), P(C.c_float), P(C.c_float), P(MotionEntry), C.c_uint32,
+                                                P(C.c_float), P(C.c_float), P(C.c_float), P(SurfaceTexel), P(DeformEntry),
+                                                C.c_uint32]),
+    "rt_temporal_deform_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rt_render_temporal_deform_device": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet),
+                                                   C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams),
+                                                   P(TemporalMotionState), C.c_uint32, P(DeformMesh), C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, P(Stats)]),
+    "rt_render_temporal_deform": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams), P(TemporalMotionState),
+                                            C.c_uint32, P(DeformMesh), P(C.c_float), P(C.c_float), P(Stats)]),
 }
 
 HOST_FUNCTIONS = {

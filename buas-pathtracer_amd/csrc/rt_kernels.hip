@@ -3833,9 +3833,12 @@ struct GbufParams {
 };
 constexpr int GB_BLOCK = 128;
 constexpr uint32_t GB_MAX_GRID = 1024;  // 4 blocks a CU; (STACK_DEPTH - STACK_LDS)*8 B*GB_BLOCK*GB_MAX_GRID = 48 MiB of spill
-__global__ void __launch_bounds__(GB_BLOCK) k_gbuffer(DevScene sc, GbufParams gp, rt_gbuffer_texel* out, uint2* spill) {
-    __shared__ uint2 lds_stack[STACK_LDS*GB_BLOCK];
-    __shared__ float2 lds_bary[GB_BLOCK];
+// One body for k_gbuffer and k_gbuffer_surface (rt_gbuffer_surface_device; DESIGN.md "Deforming meshes keep their
+// history"): SURFACE also writes, per pixel, which triangle of which vertex buffer the hit lies on and where, the very
+// (tri, v, w) hit_geometry reads.  k_gbuffer keeps its instruction count, registers, LDS and scratch.
+template <bool SURFACE>
+RT_D void gbuffer_pixels(const DevScene& sc, const GbufParams& gp, rt_gbuffer_texel* out, rt_surface_texel* surface, uint2* spill,
+                         uint2* lds_stack, float2* lds_bary) {
     Stack st;
     st.lds = lds_stack; st.spill = spill; st.bary = lds_bary; st.lane = threadIdx.x; st.block = GB_BLOCK;
     st.gtid = blockIdx.x*GB_BLOCK + threadIdx.x; st.nthreads = gridDim.x*GB_BLOCK;
@@ -3869,7 +3872,25 @@ __global__ void __launch_bounds__(GB_BLOCK) k_gbuffer(DevScene sc, GbufParams gp
             g.p = {rd.x, rd.y, rd.z}; g.t = 0.0f; g.n = {0.0f, 0.0f, 0.0f}; g.primitive = RT_HIT_MISS;
         }
         out[i] = g;
+        if (SURFACE) {
+            // h.tri and the barycentrics mean something for a mesh hit only (a miss has every bit of the code set)
+            uint4 sr = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+            if (!(h.code & RT_HIT_PLANE_BIT) && sc.prims[h.code].type == RT_PRIMITIVE_MESH)
+                sr = make_uint4(sc.tri_orig[h.tri], __float_as_uint(h.v), __float_as_uint(h.w), 0u);
+            reinterpret_cast<uint4*>(surface)[i] = sr;
+        }
     }
+}
+__global__ void __launch_bounds__(GB_BLOCK) k_gbuffer(DevScene sc, GbufParams gp, rt_gbuffer_texel* out, uint2* spill) {
+    __shared__ uint2 lds_stack[STACK_LDS*GB_BLOCK];
+    __shared__ float2 lds_bary[GB_BLOCK];
+    gbuffer_pixels<false>(sc, gp, out, nullptr, spill, lds_stack, lds_bary);
+}
+__global__ void __launch_bounds__(GB_BLOCK) k_gbuffer_surface(DevScene sc, GbufParams gp, rt_gbuffer_texel* out,
+                                                              rt_surface_texel* surface, uint2* spill) {
+    __shared__ uint2 lds_stack[STACK_LDS*GB_BLOCK];
+    __shared__ float2 lds_bary[GB_BLOCK];
+    gbuffer_pixels<true>(sc, gp, out, surface, spill, lds_stack, lds_bary);
 }
 
 // k_post — the output pass (RT/raytracer.cpp:2103-2171): resolve, exposure,
@@ -5719,6 +5740,56 @@ int rt_scene_primitive_transforms(const rt_scene* s, uint32_t cap, rt_m4x4inv* o
     return RT_OK;
 }
 
+// DESIGN.md "Deforming meshes keep their history": the rows of last frame's transforms and, for the primitives whose
+// mesh the caller lists, where last frame's vertices are.  Host only.
+int rt_scene_deform_table(const rt_scene* s, uint32_t mesh_count, const rt_deform_mesh* meshes, uint32_t primitive_count,
+                          const rt_m4x4inv* prev, rt_deform_entry* out) {
+    const std::string e = "rt_scene_deform_table";
+    if (!s) { set_error(e + ": null scene"); return RT_ERROR_INVALID; }
+    if (mesh_count && !meshes) { set_error(e + ": null meshes with a mesh_count"); return RT_ERROR_INVALID; }
+    const rt_scene::Keep& k = s->keep;
+    if (primitive_count != k.prims.size()) {
+        set_error(e + ": primitive_count " + std::to_string(primitive_count) + " is not the scene's " + std::to_string(k.prims.size()));
+        return RT_ERROR_INVALID;
+    }
+    if (primitive_count && !prev) { set_error(e + ": null prev"); return RT_ERROR_INVALID; }
+    if (primitive_count && !out) { set_error(e + ": null out"); return RT_ERROR_INVALID; }
+    std::vector<const rt_deform_mesh*> listed(k.meshes.size(), nullptr);
+    for (uint32_t j = 0; j < mesh_count; ++j) {
+        const rt_deform_mesh& m = meshes[j];
+        const std::string at = e + ": meshes[" + std::to_string(j) + "]: ";
+        if (m.mesh_index >= k.meshes.size()) {
+            set_error(at + "mesh_index " + std::to_string(m.mesh_index) + " is out of range");
+            return RT_ERROR_INVALID;
+        }
+        if (listed[m.mesh_index]) { set_error(at + "mesh " + std::to_string(m.mesh_index) + " is listed twice"); return RT_ERROR_INVALID; }
+        if (!m.d_prev_triangles) { set_error(at + "null d_prev_triangles"); return RT_ERROR_INVALID; }
+        if (k.meshes[m.mesh_index].has_normals && !m.d_prev_normals) {
+            set_error(at + "null d_prev_normals for mesh " + std::to_string(m.mesh_index) + ", which was uploaded with normals");
+            return RT_ERROR_INVALID;
+        }
+        if (!k.meshes[m.mesh_index].has_normals && m.d_prev_normals) {
+            set_error(at + "d_prev_normals for mesh " + std::to_string(m.mesh_index) + ", which was uploaded without normals");
+            return RT_ERROR_INVALID;
+        }
+        listed[m.mesh_index] = &m;
+    }
+    for (uint32_t i = 0; i < primitive_count; ++i) {
+        rt_deform_entry& o = out[i];
+        memset(&o, 0, sizeof(o));
+        memcpy(o.inv_prev, prev[i].inverse.e, sizeof(o.inv_prev));       // rows 0..2
+        memcpy(o.fwd_prev, prev[i].forward.e, sizeof(o.fwd_prev));
+        const rt_primitive& pr = k.prims[i];
+        if (pr.type != RT_PRIMITIVE_MESH || !listed[pr.mesh_index]) continue;
+        o.d_prev_triangles = listed[pr.mesh_index]->d_prev_triangles;
+        o.d_prev_normals = listed[pr.mesh_index]->d_prev_normals;
+        o.triangle_count = k.mesh_tris[pr.mesh_index];
+        o.deformed = 1u;
+        o.has_normals = k.meshes[pr.mesh_index].has_normals ? 1u : 0u;
+    }
+    return RT_OK;
+}
+
 int rt_scene_free(rt_scene* s) {
     if (!s) return RT_OK;
     (void)hipSetDevice(s->device);
@@ -6565,11 +6636,12 @@ int check_gbuffer(const char* entry, const rt_scene* s, const rt_camera* camera,
 }
 }  // namespace
 
-int rt_gbuffer_device(rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t w, uint32_t h,
-                      rt_gbuffer_texel* d_out, void* hip_stream) {
-    int err = check_gbuffer("rt_gbuffer_device", s, c, w, h, d_out, "d_out");
+namespace {
+// rt_gbuffer_device and rt_gbuffer_surface_device past their argument checks: d_surface null is the former
+int launch_gbuffer(const char* entry, rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t w, uint32_t h,
+                   rt_gbuffer_texel* d_out, rt_surface_texel* d_surface, void* hip_stream) {
+    int err = scene_stale(s, entry);
     if (err) return err;
-    if ((err = scene_stale(s, "rt_gbuffer_device"))) return err;
     err = bind_device(s->device);
     if (err) return err;
     // the spill area of the largest grid, once per scene (rt_scene_free frees it)
@@ -6586,10 +6658,52 @@ int rt_gbuffer_device(rt_scene* s, const rt_camera* c, float lens_distortion, ui
     const uint64_t blocks = ((uint64_t)w*h + GB_BLOCK - 1) / GB_BLOCK;
     const uint32_t grid = blocks < GB_MAX_GRID ? (uint32_t)blocks : GB_MAX_GRID;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    k_gbuffer<<<grid, GB_BLOCK, 0, stream>>>(s->ds, gp, d_out, s->gbuf_spill);
+    if (d_surface) k_gbuffer_surface<<<grid, GB_BLOCK, 0, stream>>>(s->ds, gp, d_out, d_surface, s->gbuf_spill);
+    else k_gbuffer<<<grid, GB_BLOCK, 0, stream>>>(s->ds, gp, d_out, s->gbuf_spill);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(stream));
     return RT_OK;
+}
+}  // namespace
+
+int rt_gbuffer_device(rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t w, uint32_t h,
+                      rt_gbuffer_texel* d_out, void* hip_stream) {
+    int err = check_gbuffer("rt_gbuffer_device", s, c, w, h, d_out, "d_out");
+    if (err) return err;
+    return launch_gbuffer("rt_gbuffer_device", s, c, lens_distortion, w, h, d_out, nullptr, hip_stream);
+}
+
+int rt_gbuffer_surface_device(rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t w, uint32_t h,
+                              rt_gbuffer_texel* d_out, rt_surface_texel* d_surface, void* hip_stream) {
+    int err = check_gbuffer("rt_gbuffer_surface_device", s, c, w, h, d_out, "d_out");
+    if (err) return err;
+    if (!d_surface) { set_error("rt_gbuffer_surface_device: null d_surface"); return RT_ERROR_INVALID; }
+    return launch_gbuffer("rt_gbuffer_surface_device", s, c, lens_distortion, w, h, d_out, d_surface, hip_stream);
+}
+
+int rt_gbuffer_surface(rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t w, uint32_t h, rt_gbuffer_texel* out,
+                       rt_surface_texel* surface) {
+    int err = check_gbuffer("rt_gbuffer_surface", s, c, w, h, out, "out");
+    if (err) return err;
+    if (!surface) { set_error("rt_gbuffer_surface: null surface"); return RT_ERROR_INVALID; }
+    err = bind_device(s->device);
+    if (err) return err;
+    const size_t n = (size_t)w*h;
+    char* d = nullptr;
+    if (hipMalloc(&d, (sizeof(rt_gbuffer_texel) + sizeof(rt_surface_texel))*n) != hipSuccess) {
+        set_error("rt_gbuffer_surface: hipMalloc");
+        return RT_ERROR_OUT_OF_MEMORY;
+    }
+    rt_gbuffer_texel* d_o = reinterpret_cast<rt_gbuffer_texel*>(d);
+    rt_surface_texel* d_s = reinterpret_cast<rt_surface_texel*>(d + sizeof(rt_gbuffer_texel)*n);
+    err = rt_gbuffer_surface_device(s, c, lens_distortion, w, h, d_o, d_s, nullptr);
+    if (!err && (hipMemcpy(out, d_o, sizeof(rt_gbuffer_texel)*n, hipMemcpyDeviceToHost) != hipSuccess ||
+                 hipMemcpy(surface, d_s, sizeof(rt_surface_texel)*n, hipMemcpyDeviceToHost) != hipSuccess)) {
+        set_error("rt_gbuffer_surface: copy out");
+        err = RT_ERROR_DEVICE;
+    }
+    (void)hipFree(d);
+    return err;
 }
 
 int rt_gbuffer(rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t w, uint32_t h, rt_gbuffer_texel* out) {

@@ -1103,6 +1103,99 @@ enum rt_mesh_table {
 int rt_debug_scene_mesh_table(const rt_scene* scene, uint32_t mesh_index, int which, void* out, size_t cap,
                               size_t* out_bytes);
 
+/* A temporal history that follows deforming meshes (beyond the reference, an opt-in: new entries only, no other
+ * entry's behaviour changes; RT_ABI_VERSION stays).  DESIGN.md ("Deforming meshes keep their history") defines the
+ * stage operation by operation; its kernel matches tests/ref_deform/ref_deform.c bit for bit.
+ *
+ * The surface record: beside each G-buffer texel, which triangle the primary hit lies on and where.  For a hit on a
+ * mesh primitive `triangle` is the mesh-local ORIGINAL index (the order of rt_mesh::normals and of
+ * rt_scene_update_mesh_device's input) and v, w are the hit's barycentrics, the floats the shading normal is
+ * interpolated with (u = 1 - v - w belongs to the triangle's first vertex).  Every other pixel (a miss, a plane, a
+ * sphere, a box) holds {0xFFFFFFFF, 0, 0, 0}. */
+typedef struct rt_surface_texel { uint32_t triangle; float v, w; uint32_t reserved; } rt_surface_texel;  /* 16 B */
+/* rt_gbuffer_device with the record: d_out receives rt_gbuffer_device's texels bit for bit, d_surface w*h records.
+ * The same fixed grid, spill area and refusals, plus a NULL d_surface. */
+int rt_gbuffer_surface_device(rt_scene* scene, const rt_camera* camera, float lens_distortion, uint32_t w, uint32_t h,
+                              rt_gbuffer_texel* d_out, rt_surface_texel* d_surface, void* hip_stream);
+/* Same, into host memory. */
+int rt_gbuffer_surface(rt_scene* scene, const rt_camera* camera, float lens_distortion, uint32_t w, uint32_t h,
+                       rt_gbuffer_texel* out, rt_surface_texel* surface);
+
+/* The deform table.  A caller lists, per frame, the meshes it deformed since the previous frame, each with the
+ * vertex buffer (and normals) the PREVIOUS frame was rendered with: the arrays it gave the update before the last
+ * one (or the upload's, in original order), still on the scene's device.  The caller double-buffers. */
+typedef struct rt_deform_mesh {
+    uint32_t     mesh_index, reserved;
+    const float* d_prev_triangles;     /* 9 floats a triangle, original order, on the scene's device */
+    const float* d_prev_normals;       /* 9 floats a triangle, or NULL for a mesh uploaded without normals */
+} rt_deform_mesh;
+typedef struct rt_deform_entry {       /* 128 B, one per primitive */
+    float        inv_prev[3][4], fwd_prev[3][4];    /* rows 0..2 of the previous frame's inverse and forward */
+    const float* d_prev_triangles;
+    const float* d_prev_normals;
+    uint32_t     triangle_count, deformed, has_normals, reserved;
+} rt_deform_entry;
+/* out[i], i < primitive_count, from prev[i] (what rt_scene_primitive_transforms returned the frame before).  A mesh
+ * primitive whose mesh_index is listed takes deformed = 1, the two pointers, the mesh's triangle count and
+ * has_normals from the scene's host copies; every other entry has deformed = 0, NULL pointers and 0 counts.  Host
+ * only, no device work.  RT_ERROR_INVALID by name: a NULL scene, NULL meshes with a mesh_count, NULL prev or out with
+ * a primitive_count, a primitive_count other than the scene's, a mesh_index out of range or listed twice, NULL
+ * d_prev_triangles, NULL d_prev_normals for a mesh uploaded with normals or non-NULL for one without. */
+int rt_scene_deform_table(const rt_scene* scene, uint32_t mesh_count, const rt_deform_mesh* meshes,
+                          uint32_t primitive_count, const rt_m4x4inv* prev, rt_deform_entry* out);
+
+/* The deform-aware accumulate stage: rt_temporal_accumulate_motion_device's arguments and operations with one more
+ * case, taken before the motion case.  For a hit without RT_HIT_PLANE_BIT whose primitive is below deform_count, whose
+ * entry e has deformed != 0 and whose surface record has triangle < e.triangle_count, with a', b', c' the nine floats
+ * at e.d_prev_triangles + 9*triangle:
+ *   e1 = b' - a';  e2 = c' - a';  Po.k = (a'.k + v*e1.k) + w*e2.k
+ *   Q.k = ((f[k][0]*Po.x + f[k][1]*Po.y) + f[k][2]*Po.z) + f[k][3],  f = fwd_prev
+ *   no = has_normals ? (u*n0 + v*n1) + w*n2 with u = 1 - v - w and n0..n2 at e.d_prev_normals + 9*triangle
+ *                    : cross(normalize(e1), normalize(e2))
+ *   n' = the shading normal of `no` under inv_prev (the renderer's transform_normal, then its normalize-or-zero)
+ * and Q and n' stand where P and the texel's n stand in the projection and in the tap tests: they are the p and n
+ * the previous G-buffer held for this surface point.  plane_limit stays plane_tolerance * t.  Every other pixel
+ * takes rt_temporal_accumulate_motion_device's path word for word.  d_deform NULL requires deform_count 0 and allows a
+ * NULL d_surface; a table requires d_surface.  The other refusals are the motion stage's. */
+int rt_temporal_accumulate_deform_device(int device, const float* d_current, const rt_gbuffer_texel* d_gbuffer,
+                                         const float* d_prev_history, const float* d_prev_length,
+                                         const rt_gbuffer_texel* d_prev_gbuffer, const rt_camera* prev_camera,
+                                         float prev_lens_distortion, uint32_t w, uint32_t h,
+                                         const rt_temporal_params* p, float* d_history, float* d_length,
+                                         void* hip_stream, const rt_motion_entry* d_motion, uint32_t motion_count,
+                                         const float* d_prev_moments, float* d_moments, float* d_velocity,
+                                         const rt_surface_texel* d_surface, const rt_deform_entry* d_deform,
+                                         uint32_t deform_count);
+/* Same on host buffers; the table's entries are on the host, the vertex pointers inside them stay device pointers. */
+int rt_temporal_accumulate_deform(int device, const float* current, const rt_gbuffer_texel* gbuffer,
+                                  const float* prev_history, const float* prev_length,
+                                  const rt_gbuffer_texel* prev_gbuffer, const rt_camera* prev_camera,
+                                  float prev_lens_distortion, uint32_t w, uint32_t h, const rt_temporal_params* p,
+                                  float* history, float* length, const rt_motion_entry* motion,
+                                  uint32_t motion_count, const float* prev_moments, float* moments, float* velocity,
+                                  const rt_surface_texel* surface, const rt_deform_entry* deform,
+                                  uint32_t deform_count);
+
+/* The driver: rt_render_temporal_motion_device's frame, state and arguments with rt_gbuffer_surface_device in place
+ * of rt_gbuffer_device, rt_scene_deform_table against state->transforms beside rt_motion_table, and the deform stage
+ * in place of the motion stage.  The workspace is rt_temporal_motion_workspace_bytes, then one surface buffer of 16 B
+ * a pixel, then the deform table of 128 B a primitive.  `meshes` lists what deformed since the previous frame, with
+ * the buffers the previous frame's update was given; the list is checked on every frame, also on one that runs
+ * without history.  A frame's order for the caller: rt_scene_update_mesh_device with the new vertices, the top-level
+ * BVH and rt_scene_update_instances, then this driver. */
+size_t rt_temporal_deform_workspace_bytes(uint32_t w, uint32_t h, uint32_t primitive_count);   /* no device needed */
+int rt_render_temporal_deform_device(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                                     const rt_filter_cache* filter, const rt_tile_set* tiles,
+                                     uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
+                                     const rt_temporal_params* p, rt_temporal_motion_state* state,
+                                     uint32_t mesh_count, const rt_deform_mesh* meshes, float* d_out,
+                                     float* d_length_out, void* hip_stream, rt_stats* stats);
+int rt_render_temporal_deform(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                              const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                              uint32_t w, uint32_t h, uint32_t frame_count, const rt_temporal_params* p,
+                              rt_temporal_motion_state* state, uint32_t mesh_count, const rt_deform_mesh* meshes,
+                              float* out_pixels, float* out_length, rt_stats* stats);
+
 /* The reference's top-down BVH builders on the device (RT/bvh.cpp:222-326 with
  * partition_midpoint :53-61, partition_sah_binned :138-213 or the full SAH sweep
  * partition_objects_sah / evaluate_sah :63-131, the partition of :26-51): one launch per
