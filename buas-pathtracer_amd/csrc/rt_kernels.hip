@@ -5636,7 +5636,9 @@ int rt_scene_upload(const rt_scene_desc* d, int device, rt_scene** out) {
     ds.bot_sky = rv3(d->bot_sky_color);
     if ((err = upload(s, rt_dev_strata_tab, sizeof(rt_dev_strata_tab), &ds.strata))) return fail(err);
     if ((err = upload(s, rt_dev_bluenoise_tab, sizeof(rt_dev_bluenoise_tab), &ds.bluenoise))) return fail(err);
-    if (debug_timing())
+    // (read at this upload like the switches above, not through debug_timing()'s once-per-process answer:
+    // a process that uploaded before RT_DEBUG_TIMING was set still gets this line)
+    if (getenv("RT_DEBUG_TIMING"))
         fprintf(stderr, "[rt timing] rt_scene_upload: scene tables %zu B (%s LDS; materials %zu, primitives %u, planes %u, "
                 "transforms %zu, lights %u, meshes %zu)\n", it.blob.size(), ds.blob_q ? "in" : "not in", mats.size(),
                 d->primitive_count, d->plane_count, it.inv.size(), d->light_count, meshes.size());
