@@ -4,12 +4,13 @@
 // moments (rt_temporal_variance_device), an à-trous filter whose colour term is scaled by that variance and whose
 // edge-stopping terms come from the G-buffer (rt_denoise_variance_device), and the driver that runs one frame of
 // the loop (rt_render_temporal_filtered_device).  Beyond the reference, an opt-in: no other entry
-// calls it, and rt_render_temporal_device is not touched.
+// calls it.
 //
 // The stage is defined operation by operation in DESIGN.md ("Variance-guided filtering"); tests/ref_svgf/
 // ref_svgf.c restates it in plain C and the kernels below match that checker bit for bit: IEEE f32, no contraction,
 // division as /, correctly rounded sqrt, the exponential d_expf (the oracle's oracle_expf), and the additions in
-// the stated orders.
+// the stated orders.  k_temporal_accumulate_moments' text is rt_temporal_shared.h's one accumulate body with the
+// moments flag on and neither table.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -18,20 +19,14 @@
 #include "rt_abi.h"
 #include "rt_internal.h"
 #include "rt_dmath.h"
-#include "rt_temporal_shared.h"   // the projection, the tap rule and the accumulate stage's argument checks
+#include "rt_temporal_shared.h"   // the accumulate body and what the stage's entries and the drivers share on the host
 
 namespace {
 
 constexpr float INVALID_L = -1.0f;      // the filter's mark of an invalid pixel in {r, g, b, l}; l >= 0 otherwise
 constexpr float INVALID_VAR = -1.0f;    // and in the variance buffer beside it; a valid variance is >= 0
 
-// tm(c) = 1 - expf(-lum(c)): the denoise stage's l, in [0, 1]
-__device__ __forceinline__ float tm_of(float r, float g, float b) {
-    const float y = (0.2126f*r + 0.7152f*g) + 0.0722f*b;
-    return 1.0f - rtd::d_expf(-y);
-}
-
-// ---- 1. accumulate with moments: k_temporal_accumulate (rt_temporal.hip) step by step, and {m1, m2} beside it
+// ---- 1. accumulate with moments: the shared body with {m1, m2} beside the history, and neither table
 
 __global__ void __launch_bounds__(256) k_temporal_accumulate_moments(const float4* __restrict__ current,
                                                                      const rt_gbuffer_texel* __restrict__ gbuffer,
@@ -42,78 +37,8 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate_moments(const float
                                                                      uint32_t w, uint32_t h, rt_temporal_params p,
                                                                      float4* __restrict__ history, float* __restrict__ length,
                                                                      float2* __restrict__ moments) {
-    const uint32_t x = blockIdx.x*64 + (threadIdx.x & 63), y = blockIdx.y*4 + (threadIdx.x >> 6);
-    if (x >= w || y >= h) return;
-    const size_t i = (size_t)y*w + x;
-    // 1. validity: the denoise stage's rule
-    const float4 s = current[i];
-    bool valid = s.w > VALID_W;
-    float cr = 0.0f, cg = 0.0f, cb = 0.0f;
-    if (valid) {
-        cr = s.x / s.w; cg = s.y / s.w; cb = s.z / s.w;
-        valid = finite_f(cr) && finite_f(cg) && finite_f(cb);
-    }
-    if (!valid) {
-        history[i] = s;
-        length[i] = 0.0f;
-        moments[i] = make_float2(0.0f, 0.0f);
-        return;
-    }
-    // 2. clamp
-    cr = cr > 0.0f ? cr : 0.0f; cg = cg > 0.0f ? cg : 0.0f; cb = cb > 0.0f ? cb : 0.0f;
-    if (p.firefly_clamp > 0.0f) {
-        cr = cr < p.firefly_clamp ? cr : p.firefly_clamp;
-        cg = cg < p.firefly_clamp ? cg : p.firefly_clamp;
-        cb = cb < p.firefly_clamp ? cb : p.firefly_clamp;
-    }
-    const float t = tm_of(cr, cg, cb), t2 = t*t;
-    TapSum sum = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    MomentSum ms = {0.0f, 0.0f};
-    if (prev_history) {
-        // 3. the point and its place in the previous frame
-        const rt_gbuffer_texel g = gbuffer[i];
-        V3f P = v3_of(g.p);
-        if (g.primitive == RT_HIT_MISS) P = {cam.p.x + g.p.x, cam.p.y + g.p.y, cam.p.z + g.p.z};
-        float fx, fy;
-        if (project_prev(cam, P, w, h, fx, fy)) {
-            // 4. the taps
-            const float plane_limit = p.plane_tolerance*g.t;
-            const float rx = rintf(fx), ry = rintf(fy);
-            if (fabsf(fx - rx) <= p.snap && fabsf(fy - ry) <= p.snap) {
-                add_tap_moments(sum, ms, (int)rx, (int)ry, 1.0f, w, h, prev_history, prev_length, prev_gbuffer, prev_moments, g, P, p.normal_cos, plane_limit);
-            } else {
-                const float x0 = floorf(fx), y0 = floorf(fy);
-                const float tx = fx - x0, ty = fy - y0;
-                const int ix = (int)x0, iy = (int)y0;
-                add_tap_moments(sum, ms, ix, iy, (1.0f - tx)*(1.0f - ty), w, h, prev_history, prev_length, prev_gbuffer, prev_moments, g, P, p.normal_cos, plane_limit);
-                add_tap_moments(sum, ms, ix + 1, iy, tx*(1.0f - ty), w, h, prev_history, prev_length, prev_gbuffer, prev_moments, g, P, p.normal_cos, plane_limit);
-                add_tap_moments(sum, ms, ix, iy + 1, (1.0f - tx)*ty, w, h, prev_history, prev_length, prev_gbuffer, prev_moments, g, P, p.normal_cos, plane_limit);
-                add_tap_moments(sum, ms, ix + 1, iy + 1, tx*ty, w, h, prev_history, prev_length, prev_gbuffer, prev_moments, g, P, p.normal_cos, plane_limit);
-            }
-        }
-    }
-    // 5. the blend
-    if (sum.W > 0.0f) {
-        const float hr = sum.r / sum.W, hg = sum.g / sum.W, hb = sum.b / sum.W;
-        const float L = sum.L / sum.W;
-        const float h1 = ms.S1 / sum.W, h2 = ms.S2 / sum.W;
-        float N = L + 1.0f;
-        N = N < p.max_history ? N : p.max_history;
-        const float a = 1.0f / N;
-        // N = 1 (max_history = 1: a valid tap's length is >= 1) is the current frame itself, not hist + (c - hist)
-        if (N == 1.0f) {
-            history[i] = make_float4(cr, cg, cb, 1.0f);
-            moments[i] = make_float2(t, t2);
-        } else {
-            history[i] = make_float4(hr + (cr - hr)*a, hg + (cg - hg)*a, hb + (cb - hb)*a, 1.0f);
-            moments[i] = make_float2(h1 + (t - h1)*a, h2 + (t2 - h2)*a);
-        }
-        length[i] = N;
-    } else {
-        history[i] = make_float4(cr, cg, cb, 1.0f);
-        length[i] = 1.0f;
-        moments[i] = make_float2(t, t2);
-    }
+    temporal_accumulate_body<true, false, false>(current, gbuffer, prev_history, prev_length, prev_gbuffer, prev_moments, cam, w, h, p,
+                                                 nullptr, 0u, nullptr, nullptr, 0u, history, length, moments, nullptr);
 }
 
 // ---- 2. the variance of the history
@@ -293,35 +218,18 @@ __global__ void __launch_bounds__(256) k_svgf_iterate(const float4* __restrict__
     }
 }
 
-TaCamera ta_camera(const rt_camera* c, float lens_distortion) {
-    TaCamera cam = {};
-    cam.p = {c->p.x, c->p.y, c->p.z};
-    cam.x = {c->x.x, c->x.y, c->x.z};
-    cam.y = {c->y.x, c->y.y, c->y.z};
-    cam.z = {c->z.x, c->z.y, c->z.z};
-    cam.film_distance = c->film_distance;
-    cam.half_film_w = c->half_film_w;
-    cam.half_film_h = c->half_film_h;
-    cam.lens_distortion = lens_distortion;
-    return cam;
-}
-
-// the accumulate stage's checks, then the moments'
-int check_moments(const std::string& e, const char* prefix, const void* current, const void* gbuffer, const void* prev_history,
-                  const void* prev_length, const void* prev_gbuffer, const void* prev_moments, const rt_camera* prev_camera,
-                  uint32_t w, uint32_t h, const rt_temporal_params* p, const void* history, const void* length,
-                  const void* moments) {
+// the accumulate stage's checks, then the moments' (mandatory here: another rule than the motion stage's)
+int check_moments(const std::string& e, const char* prefix, const TaArgs& a) {
     const std::string d = prefix;
-    if (!moments) return fail(RT_ERROR_INVALID, e + ": null " + d + "moments");
+    if (!a.moments) return fail(RT_ERROR_INVALID, e + ": null " + d + "moments");
     // all-or-none with the other three: check_accumulate names the one of those that is missing
-    const bool any = prev_history || prev_length || prev_gbuffer || prev_moments;
-    int err = check_accumulate(e, prefix, current, gbuffer, prev_history, prev_length, prev_gbuffer, prev_camera, w, h, p, history,
-                               length);
+    const bool any = a.prev_history || a.prev_length || a.prev_gbuffer || a.prev_moments;
+    int err = check_accumulate(e, prefix, a);
     if (err) return err;
     if (any) {
-        if (!prev_history) return fail(RT_ERROR_INVALID, e + ": null " + d + "prev_history beside other previous buffers");
-        if (!prev_moments) return fail(RT_ERROR_INVALID, e + ": null " + d + "prev_moments beside other previous buffers");
-        if (moments == prev_moments) return fail(RT_ERROR_INVALID, e + ": " + d + "moments aliases " + d + "prev_moments");
+        if (!a.prev_history) return fail(RT_ERROR_INVALID, e + ": null " + d + "prev_history beside other previous buffers");
+        if (!a.prev_moments) return fail(RT_ERROR_INVALID, e + ": null " + d + "prev_moments beside other previous buffers");
+        if (a.moments == a.prev_moments) return fail(RT_ERROR_INVALID, e + ": " + d + "moments aliases " + d + "prev_moments");
     }
     return RT_OK;
 }
@@ -447,25 +355,14 @@ int rt_temporal_accumulate_moments_device(int device, const float* d_current, co
                                           const rt_camera* prev_camera, float prev_lens_distortion, uint32_t w, uint32_t h,
                                           const rt_temporal_params* p, float* d_history, float* d_length, float* d_moments,
                                           void* hip_stream) {
-    int err = check_moments("rt_temporal_accumulate_moments_device", "d_", d_current, d_gbuffer, d_prev_history, d_prev_length,
-                            d_prev_gbuffer, d_prev_moments, prev_camera, w, h, p, d_history, d_length, d_moments);
+    const std::string e = "rt_temporal_accumulate_moments_device";
+    const TaArgs a = {d_current, d_gbuffer, d_prev_history, d_prev_length, d_prev_gbuffer, prev_camera, prev_lens_distortion,
+                      w, h, p, d_history, d_length, nullptr, 0u, d_prev_moments, d_moments};
+    int err = check_moments(e, "d_", a);
     if (err) return err;
-    err = rt_internal_bind_device(device);
-    if (err) return err;
-    TaCamera cam = {};
-    if (d_prev_history) cam = ta_camera(prev_camera, prev_lens_distortion);
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const dim3 grid((w + 63) / 64, (h + 3) / 4);
-    k_temporal_accumulate_moments<<<grid, 256, 0, stream>>>(reinterpret_cast<const float4*>(d_current), d_gbuffer,
-                                                            reinterpret_cast<const float4*>(d_prev_history), d_prev_length,
-                                                            d_prev_gbuffer, reinterpret_cast<const float2*>(d_prev_moments), cam,
-                                                            w, h, *p, reinterpret_cast<float4*>(d_history), d_length,
-                                                            reinterpret_cast<float2*>(d_moments));
-    hipError_t herr = hipGetLastError();
-    if (herr == hipSuccess) herr = hipStreamSynchronize(stream);
-    if (herr != hipSuccess)
-        return fail(RT_ERROR_DEVICE, std::string("rt_temporal_accumulate_moments_device: ") + hipGetErrorString(herr));
-    return RT_OK;
+    return launch_accumulate(e, device, k_temporal_accumulate_moments, w, h, hip_stream, f4(d_current), d_gbuffer,
+                             f4(d_prev_history), d_prev_length, d_prev_gbuffer, f2(d_prev_moments), ta_camera(a), w, h, *p,
+                             f4(d_history), d_length, f2(d_moments));
 }
 
 int rt_temporal_accumulate_moments(int device, const float* current, const rt_gbuffer_texel* gbuffer, const float* prev_history,
@@ -473,8 +370,8 @@ int rt_temporal_accumulate_moments(int device, const float* current, const rt_gb
                                    const rt_camera* prev_camera, float prev_lens_distortion, uint32_t w, uint32_t h,
                                    const rt_temporal_params* p, float* history, float* length, float* moments) {
     const std::string e = "rt_temporal_accumulate_moments";
-    int err = check_moments(e, "", current, gbuffer, prev_history, prev_length, prev_gbuffer, prev_moments, prev_camera, w, h, p,
-                            history, length, moments);
+    int err = check_moments(e, "", {current, gbuffer, prev_history, prev_length, prev_gbuffer, prev_camera, prev_lens_distortion,
+                                    w, h, p, history, length, nullptr, 0u, prev_moments, moments});
     if (err) return err;
     err = rt_internal_bind_device(device);
     if (err) return err;
@@ -651,13 +548,9 @@ int rt_render_temporal_filtered_device(rt_scene* s, const rt_camera* camera, con
     // a state of another frame size restarts
     const bool prev = state->frames != 0u && state->w == w && state->h == h;
 
-    if (hipMemsetAsync(ws.current, 0, 16*n, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
-        return fail(RT_ERROR_DEVICE, e + ": hipMemset");
     rt_stats fs;
-    err = rt_render_device(s, camera, st, filter, tiles, total_frame_index, w, h, frame_count, ws.current, hip_stream, &fs);
+    err = render_current(e, s, camera, st, filter, tiles, total_frame_index, w, h, frame_count, ws.current, hip_stream, &fs);
     if (err) return err;
-    // a frame clears the scene's cancel flag when its loop starts: one raised after it is seen here
-    if (rt_internal_scene_cancelled(s)) return fail(RT_ERROR_CANCELLED, "render cancelled");
     err = rt_gbuffer_device(s, camera, st->lens_distortion, w, h, ws.gbuffer[cur], hip_stream);
     if (err) return err;
     err = rt_temporal_accumulate_moments_device(device, ws.current, ws.gbuffer[cur], prev ? ws.history[old] : nullptr,
@@ -677,11 +570,7 @@ int rt_render_temporal_filtered_device(rt_scene* s, const rt_camera* camera, con
         (d_variance_out && hipMemcpyAsync(d_variance_out, ws.variance, 4*n, hipMemcpyDeviceToDevice, stream) != hipSuccess) ||
         hipStreamSynchronize(stream) != hipSuccess)
         return fail(RT_ERROR_DEVICE, e + ": copy out");
-    state->w = w; state->h = h;
-    state->camera = *camera;
-    state->lens_distortion = st->lens_distortion;
-    state->parity = old;
-    state->frames += 1u;
+    advance_state(state, w, h, camera, st);
     if (stats) *stats = fs;
     return RT_OK;
 }
