@@ -25,7 +25,7 @@ from .abi import (V3, v3, M4x4Inv, Material, Camera, Settings, FilterCache, Post
                   AccumulationBuffer, RayQuery, HitRecord, BvhInfo, DenoiseParams, DenoiseFeaturesParams,
                   TileErrorParams, AdaptiveParams, RobustParams, GBufferTexel, TemporalParams, TemporalState,
                   DenoiseVarianceParams, TemporalFilteredState, MotionEntry, TemporalMotionState, SurfaceTexel,
-                  DeformMesh, DeformEntry)
+                  DeformMesh, DeformEntry, NeighbourhoodTexel, TemporalClipParams)
 
 __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settings", "load_reconstruction_kernel",
            "translate", "scale", "rotate_x", "rotate_y", "rotate_z", "identity", "aim_camera", "aim_camera_at",
@@ -43,7 +43,9 @@ __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settin
            "denoise_variance_device", "MotionEntry", "TemporalMotionState", "motion_table", "temporal_accumulate_motion",
            "temporal_accumulate_motion_device", "temporal_motion_workspace_bytes", "SurfaceTexel", "DeformMesh",
            "DeformEntry", "deform_meshes", "temporal_deform_workspace_bytes", "temporal_accumulate_deform",
-           "temporal_accumulate_deform_device"]
+           "temporal_accumulate_deform_device", "NeighbourhoodTexel", "TemporalClipParams", "default_temporal_clip_params",
+           "temporal_neighbourhood", "temporal_neighbourhood_device", "temporal_accumulate_clip",
+           "temporal_accumulate_clip_device", "temporal_clipped_workspace_bytes"]
 
 PI_32 = 3.14159265359
 DEG_TO_RAD = 6.28318530717 / 360.0
@@ -786,6 +788,48 @@ class DeviceScene:
                                                       C.c_void_p(stream) if stream else None, C.byref(stats)))
         return stats
 
+    def render_temporal_clipped(self, camera, settings, filter_cache, w, h, state, meshes=(), params=None, clip_params=None,
+                                frame_count=0, total_frame_index=0, tile=64, shard_index=0, shard_count=1, want_length=True,
+                                want_clip_amount=True):
+        """rt_render_temporal_clipped: render_temporal_deform with the history clipped to the current frame's
+        neighbourhood before the blend.  `state` is a TemporalMotionState whose d_workspace points at
+        temporal_clipped_workspace_bytes(w, h, primitive count) bytes; `clip_params` a TemporalClipParams (None: the
+        defaults) -> (history, length or None, clip amount (h, w) or None, the beauty frame's stats)."""
+        if params is None:
+            params = default_temporal_params()
+        if clip_params is None:
+            clip_params = default_temporal_clip_params()
+        out = np.zeros((h, w, 4), np.float32)
+        length = np.zeros((h, w), np.float32) if want_length else None
+        amount = np.zeros((h, w), np.float32) if want_clip_amount else None
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        arr = deform_meshes(meshes)
+        fp = C.POINTER(C.c_float)
+        _check(lib().rt_render_temporal_clipped(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                                C.byref(tiles), total_frame_index, w, h, frame_count, C.byref(params),
+                                                C.byref(state), len(arr), arr if len(arr) else None, C.byref(clip_params),
+                                                out.ctypes.data_as(fp), length.ctypes.data_as(fp) if want_length else None,
+                                                amount.ctypes.data_as(fp) if want_clip_amount else None, C.byref(stats)))
+        return out, length, amount, stats
+
+    def render_temporal_clipped_device(self, camera, settings, filter_cache, w, h, params, state, meshes, clip_params, d_out,
+                                       d_length_out=None, d_clip_amount_out=None, stream=None, frame_count=0,
+                                       total_frame_index=0, tile=64, shard_index=0, shard_count=1):
+        """rt_render_temporal_clipped_device into device pointers (as render_temporal_deform_device); `clip_params` a
+        TemporalClipParams or None (a null pointer, which the entry refuses) -> the beauty frame's stats."""
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        arr = deform_meshes(meshes)
+        vp = lambda a: C.c_void_p(a) if a else None
+        _check(lib().rt_render_temporal_clipped_device(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                                       C.byref(tiles), total_frame_index, w, h, frame_count,
+                                                       C.byref(params), C.byref(state), len(arr),
+                                                       arr if len(arr) else None,
+                                                       None if clip_params is None else C.byref(clip_params), vp(d_out),
+                                                       vp(d_length_out), vp(d_clip_amount_out), vp(stream), C.byref(stats)))
+        return stats
+
     def render_temporal_filtered(self, camera, settings, filter_cache, w, h, state, params=None, filter_params=None,
                                  spatial_below=abi.RT_TEMPORAL_SPATIAL_BELOW_DEFAULT, frame_count=0, total_frame_index=0,
                                  tile=64, shard_index=0, shard_count=1, want_extras=True):
@@ -1225,6 +1269,109 @@ def temporal_accumulate_deform_device(d_current, d_gbuffer, d_prev_history, d_pr
                                                       vp(d_length), vp(stream), vp(d_motion), motion_count,
                                                       vp(d_prev_moments), vp(d_moments), vp(d_velocity), vp(d_surface),
                                                       vp(d_deform), deform_count))
+
+
+def default_temporal_clip_params():
+    """rt_temporal_clip_default_params (no device needed) -> TemporalClipParams."""
+    p = TemporalClipParams()
+    _check(lib().rt_temporal_clip_default_params(C.byref(p)))
+    return p
+
+
+def temporal_clipped_workspace_bytes(w, h, primitive_count):
+    """rt_temporal_clipped_workspace_bytes (no device needed): temporal_deform_workspace_bytes, the neighbourhood texels
+    and the clip amounts."""
+    return int(lib().rt_temporal_clipped_workspace_bytes(w, h, primitive_count))
+
+
+def temporal_neighbourhood(current, radius, firefly_clamp, device=0):
+    """The statistics of the current frame's windows on the GPU (rt_temporal_neighbourhood): a host accumulation buffer
+    (h, w, 4) -> a structured array (h, w) of abi.NEIGHBOURHOOD_DTYPE {mean, count, sigma, reserved}."""
+    current = np.ascontiguousarray(current, np.float32)
+    h, w, _ = current.shape
+    out = np.zeros((h, w), abi.NEIGHBOURHOOD_DTYPE)
+    _check(lib().rt_temporal_neighbourhood(device, current.ctypes.data_as(C.POINTER(C.c_float)), w, h, int(radius),
+                                           float(firefly_clamp), out.ctypes.data_as(C.POINTER(NeighbourhoodTexel))))
+    return out
+
+
+def temporal_neighbourhood_device(d_current, w, h, radius, firefly_clamp, d_out, device=0, stream=None):
+    """rt_temporal_neighbourhood_device on device pointers: w*h float4 in, w*h 32-byte texels out."""
+    vp = lambda a: C.c_void_p(a) if a else None
+    _check(lib().rt_temporal_neighbourhood_device(device, vp(d_current), w, h, int(radius), float(firefly_clamp), vp(d_out),
+                                                  vp(stream)))
+
+
+def temporal_accumulate_clip(current, gbuffer, prev=None, prev_camera=None, prev_lens_distortion=0.0, params=None,
+                             motion=None, surface=None, deform=None, neighbourhood=None, gamma=0.5, min_count=2.0,
+                             want_moments=False, want_velocity=False, want_clip_amount=True, device=0):
+    """The accumulate stage with a clip on the GPU (rt_temporal_accumulate_clip): temporal_accumulate_deform's arguments,
+    `neighbourhood` (h, w) of abi.NEIGHBOURHOOD_DTYPE or None, gamma and min_count
+    -> (history, length, moments or None, velocity or None, clip amount (h, w) or None)."""
+    current = np.ascontiguousarray(current, np.float32)
+    h, w, _ = current.shape
+    gbuffer = np.ascontiguousarray(gbuffer, abi.GBUFFER_DTYPE)
+    assert gbuffer.shape == (h, w)
+    if params is None:
+        params = default_temporal_params()
+    fp, gp = C.POINTER(C.c_float), C.POINTER(GBufferTexel)
+    ph = pl = pg = pm = None
+    if prev is not None:
+        ph = np.ascontiguousarray(prev[0], np.float32)
+        pl = np.ascontiguousarray(prev[1], np.float32)
+        pg = np.ascontiguousarray(prev[2], abi.GBUFFER_DTYPE)
+        assert ph.shape == (h, w, 4) and pl.shape == (h, w) and pg.shape == (h, w)
+        if want_moments:
+            pm = np.ascontiguousarray(prev[3], np.float32)
+            assert pm.shape == (h, w, 2)
+    count = dcount = 0
+    if motion is not None:
+        motion = np.ascontiguousarray(motion, abi.MOTION_DTYPE)
+        count = motion.shape[0]
+    if deform is not None:
+        deform = np.ascontiguousarray(deform, abi.DEFORM_DTYPE)
+        dcount = deform.shape[0]
+    if surface is not None:
+        surface = np.ascontiguousarray(surface, abi.SURFACE_DTYPE)
+        assert surface.shape == (h, w)
+    if neighbourhood is not None:
+        neighbourhood = np.ascontiguousarray(neighbourhood, abi.NEIGHBOURHOOD_DTYPE)
+        assert neighbourhood.shape == (h, w)
+    history = np.zeros((h, w, 4), np.float32)
+    length = np.zeros((h, w), np.float32)
+    moments = np.zeros((h, w, 2), np.float32) if want_moments else None
+    velocity = np.zeros((h, w, 2), np.float32) if want_velocity else None
+    amount = np.zeros((h, w), np.float32) if want_clip_amount else None
+    opt = lambda a, t: None if a is None else a.ctypes.data_as(t)
+    _check(lib().rt_temporal_accumulate_clip(device, current.ctypes.data_as(fp), gbuffer.ctypes.data_as(gp), opt(ph, fp),
+                                             opt(pl, fp), opt(pg, gp),
+                                             None if prev_camera is None else C.byref(prev_camera),
+                                             float(prev_lens_distortion), w, h, C.byref(params),
+                                             history.ctypes.data_as(fp), length.ctypes.data_as(fp),
+                                             opt(motion if count else None, C.POINTER(MotionEntry)), count, opt(pm, fp),
+                                             opt(moments, fp), opt(velocity, fp), opt(surface, C.POINTER(SurfaceTexel)),
+                                             opt(deform if dcount else None, C.POINTER(DeformEntry)), dcount,
+                                             opt(neighbourhood, C.POINTER(NeighbourhoodTexel)), float(gamma),
+                                             float(min_count), opt(amount, fp)))
+    return history, length, moments, velocity, amount
+
+
+def temporal_accumulate_clip_device(d_current, d_gbuffer, d_prev_history, d_prev_length, d_prev_gbuffer, prev_camera,
+                                    prev_lens_distortion, w, h, params, d_history, d_length, d_motion=None, motion_count=0,
+                                    d_prev_moments=None, d_moments=None, d_velocity=None, d_surface=None, d_deform=None,
+                                    deform_count=0, d_neighbourhood=None, gamma=0.5, min_count=2.0, d_clip_amount=None,
+                                    device=0, stream=None):
+    """rt_temporal_accumulate_clip_device on device pointers: temporal_accumulate_deform_device's arguments, the
+    neighbourhood texels, gamma, min_count and the clip amounts (optional)."""
+    vp = lambda a: C.c_void_p(a) if a else None
+    _check(lib().rt_temporal_accumulate_clip_device(device, vp(d_current), vp(d_gbuffer), vp(d_prev_history),
+                                                    vp(d_prev_length), vp(d_prev_gbuffer),
+                                                    None if prev_camera is None else C.byref(prev_camera),
+                                                    float(prev_lens_distortion), w, h, C.byref(params), vp(d_history),
+                                                    vp(d_length), vp(stream), vp(d_motion), motion_count,
+                                                    vp(d_prev_moments), vp(d_moments), vp(d_velocity), vp(d_surface),
+                                                    vp(d_deform), deform_count, vp(d_neighbourhood), float(gamma),
+                                                    float(min_count), vp(d_clip_amount)))
 
 
 def default_denoise_variance_params():

@@ -290,6 +290,18 @@ DEFORM_DTYPE = [("inv_prev", "<f4", (3, 4)), ("fwd_prev", "<f4", (3, 4)), ("d_pr
                 ("reserved", "<u4")]
 
 
+class NeighbourhoodTexel(C.Structure):  # rt_neighbourhood_texel (neighbourhood clipping: a window's statistics), 32 bytes
+    _fields_ = [("mean", V3), ("count", C.c_float), ("sigma", V3), ("reserved", C.c_float)]
+
+
+# the numpy layout of a neighbourhood buffer: np.zeros((h, w), NEIGHBOURHOOD_DTYPE)
+NEIGHBOURHOOD_DTYPE = [("mean", "<f4", (3,)), ("count", "<f4"), ("sigma", "<f4", (3,)), ("reserved", "<f4")]
+
+
+class TemporalClipParams(C.Structure):  # rt_temporal_clip_params (neighbourhood clipping: the driver's), 16 bytes
+    _fields_ = [("radius", C.c_uint32), ("gamma", C.c_float), ("min_count", C.c_float), ("reserved", C.c_uint32)]
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("node_count", C.c_uint32), ("leaf_count", C.c_uint32), ("max_depth", C.c_uint32),
                 ("max_leaf_size", C.c_uint32)]
@@ -491,6 +503,31 @@ ABI_FUNCTIONS = {
     "rt_render_temporal_deform": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
                                             C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams), P(TemporalMotionState),
                                             C.c_uint32, P(DeformMesh), P(C.c_float), P(C.c_float), P(Stats)]),
+    "rt_temporal_neighbourhood_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
+                                                   C.c_void_p, C.c_void_p]),
+    "rt_temporal_neighbourhood": (C.c_int, [C.c_int, P(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
+                                            P(NeighbourhoodTexel)]),
+    "rt_temporal_clip_default_params": (C.c_int, [P(TemporalClipParams)]),
+    "rt_temporal_accumulate_clip_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     P(Camera), C.c_float, C.c_uint32, C.c_uint32, P(TemporalParams),
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
+    "rt_temporal_accumulate_clip": (C.c_int, [C.c_int, P(C.c_float), P(GBufferTexel), P(C.c_float), P(C.c_float),
+                                              P(GBufferTexel), P(Camera), C.c_float, C.c_uint32, C.c_uint32,
+                                              P(TemporalParams), P(C.c_float), P(C.c_float), P(MotionEntry), C.c_uint32,
+                                              P(C.c_float), P(C.c_float), P(C.c_float), P(SurfaceTexel), P(DeformEntry),
+                                              C.c_uint32, P(NeighbourhoodTexel), C.c_float, C.c_float, P(C.c_float)]),
+    "rt_temporal_clipped_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rt_render_temporal_clipped_device": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet),
+                                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams),
+                                                    P(TemporalMotionState), C.c_uint32, P(DeformMesh),
+                                                    P(TemporalClipParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    P(Stats)]),
+    "rt_render_temporal_clipped": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams), P(TemporalMotionState),
+                                             C.c_uint32, P(DeformMesh), P(TemporalClipParams), P(C.c_float), P(C.c_float),
+                                             P(C.c_float), P(Stats)]),
 }
 
 HOST_FUNCTIONS = {

@@ -34,9 +34,9 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate_deform(
         const rt_surface_texel* __restrict__ surface, const rt_deform_entry* __restrict__ deform, uint32_t deform_count,
         float4* __restrict__ history, float* __restrict__ length, float2* __restrict__ moments,
         float2* __restrict__ velocity) {
-    temporal_accumulate_body<MOMENTS, true, true>(current, gbuffer, prev_history, prev_length, prev_gbuffer, prev_moments, cam, w, h, p,
+    temporal_accumulate_body<MOMENTS, true, true, false>(current, gbuffer, prev_history, prev_length, prev_gbuffer, prev_moments, cam, w, h, p,
                                                   motion, motion_count, surface, deform, deform_count, history, length, moments,
-                                                  velocity);
+                                                  velocity, TaClip{});
 }
 
 // the driver's workspace: rt_render_temporal_motion_device's (120 bytes per pixel, then the motion table on a 16-byte

@@ -31,8 +31,8 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate_motion(
         uint32_t w, uint32_t h, rt_temporal_params p, const rt_motion_entry* __restrict__ motion, uint32_t motion_count,
         float4* __restrict__ history, float* __restrict__ length, float2* __restrict__ moments,
         float2* __restrict__ velocity) {
-    temporal_accumulate_body<MOMENTS, true, false>(current, gbuffer, prev_history, prev_length, prev_gbuffer, prev_moments, cam, w, h, p,
-                                                   motion, motion_count, nullptr, nullptr, 0u, history, length, moments, velocity);
+    temporal_accumulate_body<MOMENTS, true, false, false>(current, gbuffer, prev_history, prev_length, prev_gbuffer, prev_moments, cam, w, h, p,
+                                                   motion, motion_count, nullptr, nullptr, 0u, history, length, moments, velocity, TaClip{});
 }
 
 // the driver's workspace: rt_render_temporal_device's 120 bytes per pixel, then the table on a 16-byte boundary

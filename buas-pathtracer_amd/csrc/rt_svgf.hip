@@ -37,8 +37,8 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate_moments(const float
                                                                      uint32_t w, uint32_t h, rt_temporal_params p,
                                                                      float4* __restrict__ history, float* __restrict__ length,
                                                                      float2* __restrict__ moments) {
-    temporal_accumulate_body<true, false, false>(current, gbuffer, prev_history, prev_length, prev_gbuffer, prev_moments, cam, w, h, p,
-                                                 nullptr, 0u, nullptr, nullptr, 0u, history, length, moments, nullptr);
+    temporal_accumulate_body<true, false, false, false>(current, gbuffer, prev_history, prev_length, prev_gbuffer, prev_moments, cam, w, h, p,
+                                                 nullptr, 0u, nullptr, nullptr, 0u, history, length, moments, nullptr, TaClip{});
 }
 
 // ---- 2. the variance of the history

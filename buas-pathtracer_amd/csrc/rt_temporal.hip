@@ -25,8 +25,8 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate(const float4* __res
                                                              const rt_gbuffer_texel* __restrict__ prev_gbuffer, TaCamera cam,
                                                              uint32_t w, uint32_t h, rt_temporal_params p,
                                                              float4* __restrict__ history, float* __restrict__ length) {
-    temporal_accumulate_body<false, false, false>(current, gbuffer, prev_history, prev_length, prev_gbuffer, nullptr, cam, w, h, p,
-                                                  nullptr, 0u, nullptr, nullptr, 0u, history, length, nullptr, nullptr);
+    temporal_accumulate_body<false, false, false, false>(current, gbuffer, prev_history, prev_length, prev_gbuffer, nullptr, cam, w, h, p,
+                                                  nullptr, 0u, nullptr, nullptr, 0u, history, length, nullptr, nullptr, TaClip{});
 }
 
 }  // namespace

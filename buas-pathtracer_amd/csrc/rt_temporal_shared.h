@@ -1,7 +1,8 @@
-// rt_temporal_shared.h — the temporal accumulate stage, once, for the four files that launch it: rt_temporal.hip,
-// rt_svgf.hip, rt_motion.hip and rt_deform.hip.  The device half is the projection into the previous frame, the rule
-// that says whether a previous pixel counts as a tap, and temporal_accumulate_body<MOMENTS, MOTION, DEFORM>: steps 1
-// to 5 of DESIGN.md's "Temporal accumulation" with the moments, step 3m and step 3d behind the three flags.  Each
+// rt_temporal_shared.h — the temporal accumulate stage, once, for the five files that launch it: rt_temporal.hip,
+// rt_svgf.hip, rt_motion.hip, rt_deform.hip and rt_clip.hip.  The device half is the projection into the previous frame,
+// the rule that says whether a previous pixel counts as a tap, and temporal_accumulate_body<MOMENTS, MOTION, DEFORM,
+// CLIP>: steps 1 to 5 of DESIGN.md's "Temporal accumulation" with the moments, step 3m, step 3d and step 4c (the
+// neighbourhood clip of the history, DESIGN.md's "Neighbourhood clipping") behind the four flags.  Each
 // file's __global__ kernel is a call of that body, so a history cannot drift between the entries.  The host half is
 // what the entries share: the stage's arguments and their checks as a chain, the launch, the host staging of the
 // motion and deform entries, and the drivers' workspace prefix, checks, frame prologue and state epilogue.
@@ -144,15 +145,24 @@ __device__ __forceinline__ V3f xform_dir(const float* a, V3f v) {
     return {(a[0]*v.x + a[1]*v.y) + a[2]*v.z, (a[4]*v.x + a[5]*v.y) + a[6]*v.z, (a[8]*v.x + a[9]*v.y) + a[10]*v.z};
 }
 
-// The accumulate stage of one pixel: the body of k_temporal_accumulate <false, false, false>,
-// k_temporal_accumulate_moments <true, false, false>, k_temporal_accumulate_motion<M> <M, true, false> and
-// k_temporal_accumulate_deform<M> <M, true, true>.  One thread per pixel; a wave is 64 consecutive pixels of a row
+// what step 4c reads and writes: the current frame's neighbourhood statistics, the box's half width in sigmas, the
+// fewest window pixels a texel must hold, and where the clip's size goes (may be null).  All null and 0 without CLIP.
+struct TaClip {
+    const rt_neighbourhood_texel* neighbourhood;
+    float gamma, min_count;
+    float* clip_amount;
+};
+
+// The accumulate stage of one pixel: the body of k_temporal_accumulate <false, false, false, false>,
+// k_temporal_accumulate_moments <true, false, false, false>, k_temporal_accumulate_motion<M> <M, true, false, false>,
+// k_temporal_accumulate_deform<M> <M, true, true, false> and k_temporal_accumulate_clip<M> <M, true, true, true>.  One thread per pixel; a wave is 64 consecutive pixels of a row
 // (64 x 4 blocks, as k_post): the current frame, the texel and the outputs are contiguous runs, and under a small
 // camera motion the taps of a wave are too.  (An 8 x 8 footprint per wave measured 7 to 11 % slower at 1920x1080:
 // profiles/temporal_frame_cost.txt.)  A kernel passes null for what it has no parameter for: moments and
 // prev_moments without MOMENTS, the motion table and velocity without MOTION, surface and the deform table without
-// DEFORM; velocity may be null with MOTION too.
-template <bool MOMENTS, bool MOTION, bool DEFORM>
+// DEFORM, an empty TaClip without CLIP; velocity may be null with MOTION too, the neighbourhood and the clip amount
+// with CLIP.
+template <bool MOMENTS, bool MOTION, bool DEFORM, bool CLIP>
 __device__ __forceinline__ void temporal_accumulate_body(
         const float4* __restrict__ current, const rt_gbuffer_texel* __restrict__ gbuffer,
         const float4* __restrict__ prev_history, const float* __restrict__ prev_length,
@@ -160,7 +170,7 @@ __device__ __forceinline__ void temporal_accumulate_body(
         uint32_t w, uint32_t h, const rt_temporal_params& p, const rt_motion_entry* __restrict__ motion, uint32_t motion_count,
         const rt_surface_texel* __restrict__ surface, const rt_deform_entry* __restrict__ deform, uint32_t deform_count,
         float4* __restrict__ history, float* __restrict__ length, float2* __restrict__ moments,
-        float2* __restrict__ velocity) {
+        float2* __restrict__ velocity, const TaClip& clip) {
     const uint32_t x = blockIdx.x*64 + (threadIdx.x & 63), y = blockIdx.y*4 + (threadIdx.x >> 6);
     if (x >= w || y >= h) return;
     const size_t i = (size_t)y*w + x;
@@ -179,6 +189,7 @@ __device__ __forceinline__ void temporal_accumulate_body(
         length[i] = 0.0f;
         if (MOMENTS) moments[i] = make_float2(0.0f, 0.0f);
         if (MOTION && velocity) velocity[i] = vel;
+        if constexpr (CLIP) { if (clip.clip_amount) clip.clip_amount[i] = 0.0f; }
         return;
     }
     // 2. clamp
@@ -273,8 +284,30 @@ __device__ __forceinline__ void temporal_accumulate_body(
     }
     if (MOTION && velocity) velocity[i] = vel;
     // 5. the blend
+    float clipped = 0.0f;
     if (sum.W > 0.0f) {
-        const float hr = sum.r / sum.W, hg = sum.g / sum.W, hb = sum.b / sum.W;
+        float hr = sum.r / sum.W, hg = sum.g / sum.W, hb = sum.b / sum.W;
+        // 4c. the history clipped to the current frame's neighbourhood: mean -+ gamma*sigma per channel.  The
+        // comparisons are written so that a NaN bound leaves the value alone.
+        if constexpr (CLIP) {
+            if (clip.neighbourhood) {
+                const rt_neighbourhood_texel nt = clip.neighbourhood[i];
+                if (nt.count >= clip.min_count) {
+                    const rt_v3 m = nt.mean, sg = nt.sigma;
+                    const float br = hr, bg = hg, bb = hb;
+                    const float lr = m.x - clip.gamma*sg.x, ur = m.x + clip.gamma*sg.x;
+                    const float lg = m.y - clip.gamma*sg.y, ug = m.y + clip.gamma*sg.y;
+                    const float lb = m.z - clip.gamma*sg.z, ub = m.z + clip.gamma*sg.z;
+                    hr = hr < lr ? lr : hr; hr = hr > ur ? ur : hr;
+                    hg = hg < lg ? lg : hg; hg = hg > ug ? ug : hg;
+                    hb = hb < lb ? lb : hb; hb = hb > ub ? ub : hb;
+                    const float dr = fabsf(br - hr), dg = fabsf(bg - hg), db = fabsf(bb - hb);
+                    clipped = dr;
+                    clipped = dg > clipped ? dg : clipped;
+                    clipped = db > clipped ? db : clipped;
+                }
+            }
+        }
         const float L = sum.L / sum.W;
         float N = L + 1.0f;
         N = N < p.max_history ? N : p.max_history;
@@ -296,6 +329,7 @@ __device__ __forceinline__ void temporal_accumulate_body(
         length[i] = 1.0f;
         if (MOMENTS) moments[i] = make_float2(t, t2);
     }
+    if constexpr (CLIP) { if (clip.clip_amount) clip.clip_amount[i] = clipped; }
 }
 
 bool bad_value(float v) { return !(v >= 0.0f) || v > 3.402823466e38f; }   // negative, NaN or infinite
@@ -334,10 +368,13 @@ struct TaArgs {
     const rt_surface_texel* surface;
     const rt_deform_entry* deform;
     uint32_t deform_count;
+    const rt_neighbourhood_texel* neighbourhood;    // the clip entries' four
+    float gamma, min_count;
+    float* clip_amount;
 };
 
 // The checks are a chain, each link before the device is touched: every entry's, then the motion and deform
-// entries' (their optional moments among them), then the deform entries' own.
+// entries' (their optional moments among them), then the deform entries' own, then the clip entries' own.
 int check_accumulate(const std::string& e, const char* prefix, const TaArgs& a) {
     const std::string d = prefix;
     if (!a.current) return fail(RT_ERROR_INVALID, e + ": null " + d + "current");
@@ -386,6 +423,14 @@ int check_deform(const std::string& e, const char* prefix, const TaArgs& a) {
     return RT_OK;
 }
 
+int check_clip(const std::string& e, const char* prefix, const TaArgs& a) {
+    int err = check_deform(e, prefix, a);
+    if (err) return err;
+    if (bad_value(a.gamma)) return fail(RT_ERROR_INVALID, e + ": gamma must be finite and >= 0");
+    if (bad_value(a.min_count)) return fail(RT_ERROR_INVALID, e + ": min_count must be finite and >= 0");
+    return RT_OK;
+}
+
 // the kernels' view of the previous camera; without a history nothing reads it
 TaCamera ta_camera(const TaArgs& a) {
     TaCamera cam = {};
@@ -427,8 +472,9 @@ int launch_accumulate(const std::string& e, int device, void (*kernel)(Params...
 // The host entries of the motion and deform stages, after their checks: one device allocation, the copies in, the
 // device entry (run, which gets the arguments with device pointers in place of the host's) and the copies out.  Per
 // pixel: current 16, two G-buffers 64, two histories 32, two moments 16, velocity 8 and two lengths 8 bytes, then the
-// motion table.  with_surface (the deform entry) puts the surface records (16 bytes per pixel) in front of the motion
-// table and the deform table behind it on a 16-byte boundary.
+// motion table.  with_surface (the deform and clip entries) puts the surface records (16 bytes per pixel) in front of
+// the motion table and the deform table behind it on a 16-byte boundary.  The clip entry's neighbourhood texels (32
+// bytes per pixel) and clip amounts (4) follow all that, the texels on a 16-byte boundary, when the caller has them.
 template <class Run>
 int stage_accumulate(const std::string& e, int device, const TaArgs& a, bool with_surface, Run run) {
     int err = rt_internal_bind_device(device);
@@ -437,8 +483,11 @@ int stage_accumulate(const std::string& e, int device, const TaArgs& a, bool wit
     const size_t motion_bytes = sizeof(rt_motion_entry)*(size_t)(a.motion_count ? a.motion_count : 1u);
     const size_t motion_at = (with_surface ? 160 : 144)*n;
     const size_t deform_at = motion_at + ((motion_bytes + 15) & ~(size_t)15);
-    const size_t bytes = with_surface ? deform_at + sizeof(rt_deform_entry)*(size_t)(a.deform_count ? a.deform_count : 1u)
-                                      : motion_at + motion_bytes;
+    const size_t tables_end = with_surface ? deform_at + sizeof(rt_deform_entry)*(size_t)(a.deform_count ? a.deform_count : 1u)
+                                           : motion_at + motion_bytes;
+    const size_t texels_at = (tables_end + 15) & ~(size_t)15;
+    const size_t amount_at = texels_at + (a.neighbourhood ? sizeof(rt_neighbourhood_texel)*n : 0);
+    const size_t bytes = a.neighbourhood || a.clip_amount ? amount_at + (a.clip_amount ? 4*n : 0) : tables_end;
     char* d = nullptr;
     if (hipMalloc(&d, bytes) != hipSuccess) return fail(RT_ERROR_OUT_OF_MEMORY, e + ": hipMalloc");
     float* d_cur = reinterpret_cast<float*>(d);
@@ -450,12 +499,15 @@ int stage_accumulate(const std::string& e, int device, const TaArgs& a, bool wit
     rt_surface_texel* d_s = reinterpret_cast<rt_surface_texel*>(d + 144*n);          // with_surface only
     rt_motion_entry* d_t = reinterpret_cast<rt_motion_entry*>(d + motion_at);
     rt_deform_entry* d_e = reinterpret_cast<rt_deform_entry*>(d + deform_at);        // with_surface only
+    rt_neighbourhood_texel* d_nb = reinterpret_cast<rt_neighbourhood_texel*>(d + texels_at);     // the clip entry only
+    float* d_ca = reinterpret_cast<float*>(d + amount_at);                                       // the clip entry only
     const bool prev = a.prev_history != nullptr;
     if (hipMemcpy(d_cur, a.current, 16*n, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_g[0], a.gbuffer, 32*n, hipMemcpyHostToDevice) != hipSuccess ||
         (a.surface && hipMemcpy(d_s, a.surface, 16*n, hipMemcpyHostToDevice) != hipSuccess) ||
         (a.motion_count && hipMemcpy(d_t, a.motion, sizeof(rt_motion_entry)*(size_t)a.motion_count, hipMemcpyHostToDevice) != hipSuccess) ||
         (a.deform_count && hipMemcpy(d_e, a.deform, sizeof(rt_deform_entry)*(size_t)a.deform_count, hipMemcpyHostToDevice) != hipSuccess) ||
+        (a.neighbourhood && hipMemcpy(d_nb, a.neighbourhood, sizeof(rt_neighbourhood_texel)*n, hipMemcpyHostToDevice) != hipSuccess) ||
         (prev && (hipMemcpy(d_h[1], a.prev_history, 16*n, hipMemcpyHostToDevice) != hipSuccess ||
                   hipMemcpy(d_l[1], a.prev_length, 4*n, hipMemcpyHostToDevice) != hipSuccess ||
                   hipMemcpy(d_g[1], a.prev_gbuffer, 32*n, hipMemcpyHostToDevice) != hipSuccess ||
@@ -468,11 +520,13 @@ int stage_accumulate(const std::string& e, int device, const TaArgs& a, bool wit
     on.prev_moments = a.prev_moments ? d_m[1] : nullptr; on.moments = a.moments ? d_m[0] : nullptr;
     on.velocity = a.velocity ? d_v : nullptr;
     on.surface = a.surface ? d_s : nullptr; on.deform = a.deform_count ? d_e : nullptr;
+    on.neighbourhood = a.neighbourhood ? d_nb : nullptr; on.clip_amount = a.clip_amount ? d_ca : nullptr;
     if (!err) err = run(on);
     if (!err && (hipMemcpy(a.history, d_h[0], 16*n, hipMemcpyDeviceToHost) != hipSuccess ||
                  hipMemcpy(a.length, d_l[0], 4*n, hipMemcpyDeviceToHost) != hipSuccess ||
                  (a.moments && hipMemcpy(a.moments, d_m[0], 8*n, hipMemcpyDeviceToHost) != hipSuccess) ||
-                 (a.velocity && hipMemcpy(a.velocity, d_v, 8*n, hipMemcpyDeviceToHost) != hipSuccess)))
+                 (a.velocity && hipMemcpy(a.velocity, d_v, 8*n, hipMemcpyDeviceToHost) != hipSuccess) ||
+                 (a.clip_amount && hipMemcpy(a.clip_amount, d_ca, 4*n, hipMemcpyDeviceToHost) != hipSuccess)))
         err = fail(RT_ERROR_DEVICE, e + ": copy out");
     (void)hipFree(d);
     return err;

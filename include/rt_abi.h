@@ -1196,6 +1196,90 @@ int rt_render_temporal_deform(rt_scene* scene, const rt_camera* camera, const rt
                               rt_temporal_motion_state* state, uint32_t mesh_count, const rt_deform_mesh* meshes,
                               float* out_pixels, float* out_length, rt_stats* stats);
 
+/* Neighbourhood clipping of the temporal history against ghosting (beyond the reference, an opt-in: new entries only,
+ * no other entry's behaviour changes; RT_ABI_VERSION stays).  Variance clipping after Salvi, "An excursion in temporal
+ * supersampling" (GDC 2016), in this project's terms.  DESIGN.md ("Neighbourhood clipping") defines both stages
+ * operation by operation; the kernels match tests/ref_clip/ref_clip.c bit for bit.
+ *
+ * The statistics of the current frame: per pixel, the mean and the standard deviation of the resolved colours in the
+ * (2 radius + 1)^2 window around it.  A pixel's value is the accumulate stage's steps 1 and 2: valid when its weight
+ * is above 0.001f and its resolved colour is finite, clamped per channel to [0, firefly_clamp] (no upper clamp when
+ * firefly_clamp is 0).  An invalid pixel and a pixel outside the image add +0 to all seven sums: the three channels,
+ * their squares and a count of 1.0f per valid pixel.  Each sum is taken in the separable order: a row sum
+ * H(x, y') = ((v(x-r) + v(x-r+1)) + ...) + v(x+r) for y' = y-r .. y+r, then S = ((H(x, y-r) + H(x, y-r+1)) + ...) + H(x, y+r).
+ * With n = count > 0: mean = S1/n, var = S2/n - mean*mean, var = var > 0 ? var : 0 (a NaN goes to 0), sigma =
+ * sqrtf(var); with n = 0 the texel is all zero.  A texel is written for every pixel, invalid centres included;
+ * reserved is 0.  RT_ERROR_INVALID by name before the device is touched: a NULL buffer, w or h of 0, w*h of 2^32 or
+ * more, a radius outside 1..3, a negative or non-finite firefly_clamp, d_out equal to d_current. */
+typedef struct rt_neighbourhood_texel { rt_v3 mean; float count; rt_v3 sigma; float reserved; } rt_neighbourhood_texel;  /* 32 B */
+int rt_temporal_neighbourhood_device(int device, const float* d_current, uint32_t w, uint32_t h, uint32_t radius,
+                                     float firefly_clamp, rt_neighbourhood_texel* d_out, void* hip_stream);
+/* Same, from and to host memory.  RT_ERROR_NO_DEVICE without a GPU (after the argument checks). */
+int rt_temporal_neighbourhood(int device, const float* current, uint32_t w, uint32_t h, uint32_t radius,
+                              float firefly_clamp, rt_neighbourhood_texel* out);
+
+/* The accumulate stage with a clip: rt_temporal_accumulate_deform_device's arguments and operations with one more
+ * step, 4c, between the taps and the blend.  It runs when d_neighbourhood is non-NULL, the taps' weight W is above 0
+ * and the pixel's texel has count >= min_count.  With hist = sum / W, per channel k:
+ *   lo = mean_k - gamma*sigma_k;  hi = mean_k + gamma*sigma_k
+ *   hist_k = hist_k < lo ? lo : hist_k;  then hist_k = hist_k > hi ? hi : hist_k      (a NaN bound leaves it alone)
+ * and the blend runs on the clipped hist.  d_clip_amount (w*h floats, optional) receives the largest of the three
+ * |before - after|, and 0 for a pixel that was not clipped, had no history or is invalid.  Length, moments and
+ * velocity are the deform stage's bit for bit: the clip does not touch them.  With d_neighbourhood NULL every output is
+ * rt_temporal_accumulate_deform_device's.  The refusals are the deform stage's, plus a negative or non-finite gamma or
+ * min_count. */
+typedef struct rt_temporal_clip_params {
+    uint32_t radius;       /* of the statistics' window, 1..3 */
+    float    gamma;        /* the box's half width in standard deviations */
+    float    min_count;    /* a texel with fewer valid window pixels does not clip */
+    uint32_t reserved;
+} rt_temporal_clip_params;
+int rt_temporal_clip_default_params(rt_temporal_clip_params* out);   /* 3, 0.5, 2; no device needed */
+int rt_temporal_accumulate_clip_device(int device, const float* d_current, const rt_gbuffer_texel* d_gbuffer,
+                                       const float* d_prev_history, const float* d_prev_length,
+                                       const rt_gbuffer_texel* d_prev_gbuffer, const rt_camera* prev_camera,
+                                       float prev_lens_distortion, uint32_t w, uint32_t h, const rt_temporal_params* p,
+                                       float* d_history, float* d_length, void* hip_stream,
+                                       const rt_motion_entry* d_motion, uint32_t motion_count,
+                                       const float* d_prev_moments, float* d_moments, float* d_velocity,
+                                       const rt_surface_texel* d_surface, const rt_deform_entry* d_deform,
+                                       uint32_t deform_count, const rt_neighbourhood_texel* d_neighbourhood, float gamma,
+                                       float min_count, float* d_clip_amount);
+/* Same on host buffers; the deform table's vertex pointers stay device pointers. */
+int rt_temporal_accumulate_clip(int device, const float* current, const rt_gbuffer_texel* gbuffer,
+                                const float* prev_history, const float* prev_length,
+                                const rt_gbuffer_texel* prev_gbuffer, const rt_camera* prev_camera,
+                                float prev_lens_distortion, uint32_t w, uint32_t h, const rt_temporal_params* p,
+                                float* history, float* length, const rt_motion_entry* motion, uint32_t motion_count,
+                                const float* prev_moments, float* moments, float* velocity,
+                                const rt_surface_texel* surface, const rt_deform_entry* deform, uint32_t deform_count,
+                                const rt_neighbourhood_texel* neighbourhood, float gamma, float min_count,
+                                float* clip_amount);
+
+/* The driver: rt_render_temporal_deform_device's frame, state and arguments with the clip.  A frame renders the
+ * current frame, writes the surface G-buffer, runs rt_temporal_neighbourhood_device on the current frame
+ * (cp->radius, p->firefly_clamp), builds and uploads the motion and deform tables, runs
+ * rt_temporal_accumulate_clip_device (cp->gamma, cp->min_count), copies the history, the length and the clip amounts
+ * (d_clip_amount_out, w*h floats; may be NULL) out and advances the state.  mesh_count 0 is the motion loop, unchanged
+ * transforms the plain one.  The workspace is rt_temporal_deform_workspace_bytes, then the neighbourhood texels on a
+ * 16-byte boundary (32 B a pixel), then the clip amounts (4 B a pixel).  rt_cancel and the refusals are the deform
+ * driver's, plus a NULL rt_temporal_clip_params, a radius outside 1..3 and a negative or non-finite gamma or
+ * min_count. */
+size_t rt_temporal_clipped_workspace_bytes(uint32_t w, uint32_t h, uint32_t primitive_count);   /* no device needed */
+int rt_render_temporal_clipped_device(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                                      const rt_filter_cache* filter, const rt_tile_set* tiles,
+                                      uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
+                                      const rt_temporal_params* p, rt_temporal_motion_state* state,
+                                      uint32_t mesh_count, const rt_deform_mesh* meshes,
+                                      const rt_temporal_clip_params* cp, float* d_out, float* d_length_out,
+                                      float* d_clip_amount_out, void* hip_stream, rt_stats* stats);
+int rt_render_temporal_clipped(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                               const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                               uint32_t w, uint32_t h, uint32_t frame_count, const rt_temporal_params* p,
+                               rt_temporal_motion_state* state, uint32_t mesh_count, const rt_deform_mesh* meshes,
+                               const rt_temporal_clip_params* cp, float* out_pixels, float* out_length,
+                               float* out_clip_amount, rt_stats* stats);
+
 /* The reference's top-down BVH builders on the device (RT/bvh.cpp:222-326 with
  * partition_midpoint :53-61, partition_sah_binned :138-213 or the full SAH sweep
  * partition_objects_sah / evaluate_sah :63-131, the partition of :26-51): one launch per
