@@ -25,7 +25,8 @@ from .abi import (V3, v3, M4x4Inv, Material, Camera, Settings, FilterCache, Post
                   AccumulationBuffer, RayQuery, HitRecord, BvhInfo, DenoiseParams, DenoiseFeaturesParams,
                   TileErrorParams, AdaptiveParams, RobustParams, GBufferTexel, TemporalParams, TemporalState,
                   DenoiseVarianceParams, TemporalFilteredState, MotionEntry, TemporalMotionState, SurfaceTexel,
-                  DeformMesh, DeformEntry, NeighbourhoodTexel, TemporalClipParams)
+                  DeformMesh, DeformEntry, NeighbourhoodTexel, TemporalClipParams, SpecularTexel2,
+                  GBufferSpecularParams)
 
 __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settings", "load_reconstruction_kernel",
            "translate", "scale", "rotate_x", "rotate_y", "rotate_z", "identity", "aim_camera", "aim_camera_at",
@@ -45,7 +46,8 @@ __all__ = ["Scene", "DeviceScene", "RenderError", "load_preset", "default_settin
            "DeformEntry", "deform_meshes", "temporal_deform_workspace_bytes", "temporal_accumulate_deform",
            "temporal_accumulate_deform_device", "NeighbourhoodTexel", "TemporalClipParams", "default_temporal_clip_params",
            "temporal_neighbourhood", "temporal_neighbourhood_device", "temporal_accumulate_clip",
-           "temporal_accumulate_clip_device", "temporal_clipped_workspace_bytes"]
+           "temporal_accumulate_clip_device", "temporal_clipped_workspace_bytes", "SpecularTexel2",
+           "GBufferSpecularParams", "default_gbuffer_specular_params", "temporal_specular_workspace_bytes"]
 
 PI_32 = 3.14159265359
 DEG_TO_RAD = 6.28318530717 / 360.0
@@ -830,6 +832,68 @@ class DeviceScene:
                                                        vp(d_length_out), vp(d_clip_amount_out), vp(stream), C.byref(stats)))
         return stats
 
+    def gbuffer_specular(self, camera, w, h, params=None, lens_distortion=0.0, want_chain=True):
+        """rt_gbuffer_specular: the G-buffer that follows the camera ray through mirrors and glass.  `params` a
+        GBufferSpecularParams (None: the defaults) -> (a structured array (h, w) of abi.GBUFFER_DTYPE, and one of
+        abi.SPECULAR_CHAIN_DTYPE {first_primitive, first_t, chain, end} or None)."""
+        if params is None:
+            params = default_gbuffer_specular_params()
+        out = np.zeros((h, w), abi.GBUFFER_DTYPE)
+        chain = np.zeros((h, w), abi.SPECULAR_CHAIN_DTYPE) if want_chain else None
+        _check(lib().rt_gbuffer_specular(self._h, C.byref(camera), float(lens_distortion), w, h, C.byref(params),
+                                         out.ctypes.data_as(C.POINTER(GBufferTexel)),
+                                         chain.ctypes.data_as(C.POINTER(SpecularTexel2)) if want_chain else None))
+        return out, chain
+
+    def gbuffer_specular_device(self, camera, w, h, params, d_out, d_chain=None, lens_distortion=0.0, stream=None):
+        """rt_gbuffer_specular_device into device pointers of w*h 32-byte texels and, optionally, w*h 16-byte side
+        records; `params` a GBufferSpecularParams or None (a null pointer, which the entry refuses)."""
+        vp = lambda a: C.c_void_p(a) if a else None
+        _check(lib().rt_gbuffer_specular_device(self._h, C.byref(camera), float(lens_distortion), w, h,
+                                                None if params is None else C.byref(params), vp(d_out), vp(d_chain),
+                                                vp(stream)))
+
+    def render_temporal_specular(self, camera, settings, filter_cache, w, h, state, params=None, specular_params=None,
+                                 clip_params=None, frame_count=0, total_frame_index=0, tile=64, shard_index=0,
+                                 shard_count=1, want_length=True):
+        """rt_render_temporal_specular: render_temporal over the specular G-buffer.  `state` is a TemporalState whose
+        d_workspace points at temporal_specular_workspace_bytes(w, h) bytes; `specular_params` a GBufferSpecularParams
+        (None: the defaults); `clip_params` a TemporalClipParams, or None for the plain accumulate stage
+        -> (history, length or None, the beauty frame's stats)."""
+        if params is None:
+            params = default_temporal_params()
+        if specular_params is None:
+            specular_params = default_gbuffer_specular_params()
+        out = np.zeros((h, w, 4), np.float32)
+        length = np.zeros((h, w), np.float32) if want_length else None
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        fp = C.POINTER(C.c_float)
+        _check(lib().rt_render_temporal_specular(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                                 C.byref(tiles), total_frame_index, w, h, frame_count, C.byref(params),
+                                                 C.byref(state), C.byref(specular_params),
+                                                 None if clip_params is None else C.byref(clip_params),
+                                                 out.ctypes.data_as(fp), length.ctypes.data_as(fp) if want_length else None,
+                                                 C.byref(stats)))
+        return out, length, stats
+
+    def render_temporal_specular_device(self, camera, settings, filter_cache, w, h, params, state, specular_params,
+                                        clip_params, d_out, d_length_out=None, stream=None, frame_count=0,
+                                        total_frame_index=0, tile=64, shard_index=0, shard_count=1):
+        """rt_render_temporal_specular_device into device pointers (as render_temporal_device); `specular_params` a
+        GBufferSpecularParams or None (a null pointer, which the entry refuses), `clip_params` a TemporalClipParams or
+        None (the plain accumulate stage) -> the beauty frame's stats."""
+        tiles = TileSet(tile, tile, shard_index, shard_count)
+        stats = Stats()
+        vp = lambda a: C.c_void_p(a) if a else None
+        _check(lib().rt_render_temporal_specular_device(self._h, C.byref(camera), C.byref(settings), C.byref(filter_cache),
+                                                        C.byref(tiles), total_frame_index, w, h, frame_count,
+                                                        C.byref(params), C.byref(state),
+                                                        None if specular_params is None else C.byref(specular_params),
+                                                        None if clip_params is None else C.byref(clip_params), vp(d_out),
+                                                        vp(d_length_out), vp(stream), C.byref(stats)))
+        return stats
+
     def render_temporal_filtered(self, camera, settings, filter_cache, w, h, state, params=None, filter_params=None,
                                  spatial_below=abi.RT_TEMPORAL_SPATIAL_BELOW_DEFAULT, frame_count=0, total_frame_index=0,
                                  tile=64, shard_index=0, shard_count=1, want_extras=True):
@@ -1282,6 +1346,18 @@ def temporal_clipped_workspace_bytes(w, h, primitive_count):
     """rt_temporal_clipped_workspace_bytes (no device needed): temporal_deform_workspace_bytes, the neighbourhood texels
     and the clip amounts."""
     return int(lib().rt_temporal_clipped_workspace_bytes(w, h, primitive_count))
+
+
+def default_gbuffer_specular_params():
+    """rt_gbuffer_specular_default_params (no device needed) -> GBufferSpecularParams."""
+    p = GBufferSpecularParams()
+    _check(lib().rt_gbuffer_specular_default_params(C.byref(p)))
+    return p
+
+
+def temporal_specular_workspace_bytes(w, h):
+    """rt_temporal_specular_workspace_bytes (no device needed): temporal_workspace_bytes and the neighbourhood texels."""
+    return int(lib().rt_temporal_specular_workspace_bytes(w, h))
 
 
 def temporal_neighbourhood(current, radius, firefly_clamp, device=0):

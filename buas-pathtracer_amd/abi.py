@@ -302,6 +302,22 @@ class TemporalClipParams(C.Structure):  # rt_temporal_clip_params (neighbourhood
     _fields_ = [("radius", C.c_uint32), ("gamma", C.c_float), ("min_count", C.c_float), ("reserved", C.c_uint32)]
 
 
+class SpecularTexel2(C.Structure):     # rt_specular_texel2 (the specular G-buffer's side record), 16 bytes
+    _fields_ = [("first_primitive", C.c_uint32), ("first_t", C.c_float), ("chain", C.c_uint32), ("end", C.c_uint32)]
+
+
+# the numpy layout of a side-record buffer: np.zeros((h, w), SPECULAR_CHAIN_DTYPE)
+SPECULAR_CHAIN_DTYPE = [("first_primitive", "<u4"), ("first_t", "<f4"), ("chain", "<u4"), ("end", "<u4")]
+# rt_specular_end
+(RT_SPECULAR_END_MISS, RT_SPECULAR_END_EMITTER, RT_SPECULAR_END_DIFFUSE, RT_SPECULAR_END_ROUGH, RT_SPECULAR_END_STACK,
+ RT_SPECULAR_END_CAP) = range(6)
+
+
+class GBufferSpecularParams(C.Structure):   # rt_gbuffer_specular_params (the specular G-buffer: the walk's), 16 bytes
+    _fields_ = [("max_events", C.c_uint32), ("reflect_threshold", C.c_float), ("roughness_max", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
 class BvhInfo(C.Structure):
     _fields_ = [("node_count", C.c_uint32), ("leaf_count", C.c_uint32), ("max_depth", C.c_uint32),
                 ("max_leaf_size", C.c_uint32)]
@@ -528,6 +544,20 @@ ABI_FUNCTIONS = {
                                              C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams), P(TemporalMotionState),
                                              C.c_uint32, P(DeformMesh), P(TemporalClipParams), P(C.c_float), P(C.c_float),
                                              P(C.c_float), P(Stats)]),
+    "rt_gbuffer_specular_default_params": (C.c_int, [P(GBufferSpecularParams)]),
+    "rt_gbuffer_specular_device": (C.c_int, [C.c_void_p, P(Camera), C.c_float, C.c_uint32, C.c_uint32,
+                                             P(GBufferSpecularParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_gbuffer_specular": (C.c_int, [C.c_void_p, P(Camera), C.c_float, C.c_uint32, C.c_uint32, P(GBufferSpecularParams),
+                                      P(GBufferTexel), P(SpecularTexel2)]),
+    "rt_temporal_specular_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rt_render_temporal_specular_device": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet),
+                                                     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams),
+                                                     P(TemporalState), P(GBufferSpecularParams), P(TemporalClipParams),
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, P(Stats)]),
+    "rt_render_temporal_specular": (C.c_int, [C.c_void_p, P(Camera), P(Settings), P(FilterCache), P(TileSet), C.c_uint32,
+                                              C.c_uint32, C.c_uint32, C.c_uint32, P(TemporalParams), P(TemporalState),
+                                              P(GBufferSpecularParams), P(TemporalClipParams), P(C.c_float), P(C.c_float),
+                                              P(Stats)]),
 }
 
 HOST_FUNCTIONS = {

@@ -143,14 +143,6 @@ int check_neighbourhood(const std::string& e, const char* prefix, const float* c
     return RT_OK;
 }
 
-int check_clip_params(const std::string& e, const rt_temporal_clip_params* cp) {
-    if (!cp) return fail(RT_ERROR_INVALID, e + ": null rt_temporal_clip_params");
-    if (cp->radius < 1u || cp->radius > 3u) return fail(RT_ERROR_INVALID, e + ": rt_temporal_clip_params: radius must be in 1..3");
-    if (bad_value(cp->gamma)) return fail(RT_ERROR_INVALID, e + ": rt_temporal_clip_params: gamma must be finite and >= 0");
-    if (bad_value(cp->min_count)) return fail(RT_ERROR_INVALID, e + ": rt_temporal_clip_params: min_count must be finite and >= 0");
-    return RT_OK;
-}
-
 // the driver's workspace: rt_render_temporal_deform_device's, then the neighbourhood texels on a 16-byte boundary and
 // the clip amounts
 struct Workspace : TaWorkspace {

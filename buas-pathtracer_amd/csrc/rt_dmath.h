@@ -129,6 +129,9 @@ RT_D V3 noz(V3 a) {
 RT_D float lerpf_(float a, float b, float t) { return a*(1.0f - t) + b*t; }
 RT_D V3 lerp3(V3 a, V3 b, float t) { return add(muls(a, 1.0f - t), muls(b, t)); }
 RT_D V3 reflect(V3 v, V3 n) { return sub(v, muls(n, 2.0f*dot(v, n))); }
+RT_D V3 refract(V3 d, V3 n, float cos_i, float cos_t, float eta) {      // RT/integrators.cpp:260-264
+    return add(smul(eta, d), muls(n, (eta*cos_i - cos_t)));
+}
 RT_D float sign_of(float x) { return x < 0.0f ? -1.0f : 1.0f; }
 RT_D float copy_sign(float v, float s) {
     return __uint_as_float((__float_as_uint(s) & 0x80000000u) | (__float_as_uint(v) & 0x7FFFFFFFu));

@@ -9,6 +9,9 @@ void rt_internal_set_error(const char* message);        // the thread's rt_last_
 int  rt_internal_bind_device(int device);               // hipSetDevice with the ABI's checks: an rt_status
 int  rt_internal_scene_device(const rt_scene* scene);   // the device rt_scene_upload put the scene on
 int  rt_internal_scene_cancelled(const rt_scene* scene); // rt_cancel's flag: set until the next frame's loop starts
+// rt_gbuffer_specular_device's refusals of its parameters, named after `entry` (the G-buffer's entries and the driver
+// over them, rt_specular.hip): an rt_status
+int  rt_internal_check_specular_params(const char* entry, const rt_gbuffer_specular_params* params);
 
 // What rt_refit.hip (rt_scene_update_mesh and its kin) needs of a scene.
 #include <stdint.h>

@@ -33,6 +33,7 @@
 #include <cerrno>
 
 #include "rt_dmath.h"
+#include "rt_internal.h"  // what this file exports to the library's other translation units (defined at its end)
 
 using namespace rtd;
 
@@ -2201,7 +2202,7 @@ RT_D bool shade_bounce(const DevScene& sc, const rt_settings& st, const SamplerS
                     ++at;
                     pool.mstack[(size_t)at*pool.n + slot] = (uint16_t)mt_id;   // moved with the path below
                 }
-                V3 fd = add(smul(eta, rd), muls(N, (eta*cos_i - cos_t)));
+                V3 fd = refract(rd, N, cos_i, cos_t, eta);
                 ro = add(I, muls(fd, EPSILON)); rd = fd;
             } else {                                                        // diffuse :718-790
                 is_spec = 0;
@@ -2459,7 +2460,7 @@ RT_D bool shade_bounce_feat(const DevScene& sc, const rt_settings& st, const Sam
             ++at;
             pool.mstack[(size_t)at*pool.n + slot] = (uint16_t)mt_id;       // moved with the path (k_shade)
         }
-        V3 fd = add(smul(eta, rd), muls(N, (eta*cos_i - cos_t)));
+        V3 fd = refract(rd, N, cos_i, cos_t, eta);
         ro = add(I, muls(fd, EPSILON)); rd = fd;
     } else {                                                                // the diffuse branch: the walk's end
         if (FEATURE == RT_FEATURE_ALBEDO) total = evaluate_material(mt, I);
@@ -3243,7 +3244,7 @@ __global__ void __launch_bounds__(DTB) k_recurse(DevScene sc, rt_settings st, Fr
                 const bool medium = m.is_participating_medium != 0;
                 if (medium || refl > 0.05f) {
                     // refracted_d as written, total internal reflection or not (:384)
-                    const V3 fd = add(smul(eta, rd), muls(N, (eta*cos_i - cos_t)));
+                    const V3 fd = refract(rd, N, cos_i, cos_t, eta);
                     V3 nd = reflect(rd, N);                             // :386-389 / :396-399
                     if (m.roughness > 0.0f)
                         nd = normalize(add(smul(1.0f + EPSILON, nd), smul(m.roughness, random_in_unit_sphere(rng))));
@@ -3891,6 +3892,131 @@ __global__ void __launch_bounds__(GB_BLOCK) k_gbuffer_surface(DevScene sc, GbufP
     __shared__ uint2 lds_stack[STACK_LDS*GB_BLOCK];
     __shared__ float2 lds_bary[GB_BLOCK];
     gbuffer_pixels<true>(sc, gp, out, surface, spill, lds_stack, lds_bary);
+}
+
+// k_gbuffer_specular — the G-buffer that follows the camera ray through mirrors and glass (rt_gbuffer_specular_device;
+// DESIGN.md "A specular G-buffer").  k_gbuffer's camera ray, grid and spill area; then a lane walks its pixel's specular
+// chain, one Traversal per event: the feature frames' vertex (shade_bounce_feat) with the majority lobe in the draw's
+// place, a perfect reflection and no throughput.  It carries the path length T, the product M of the reflections'
+// Householder matrices and a material stack of GS_STACK levels, [level][lane] in LDS (level 0 is the air and is never
+// read from there).  The texel of a walk without events is k_gbuffer's, bit for bit; after events it is the unfolded
+// point cp + T*D with the final normal under M.  A body of its own: gbuffer_pixels keeps its text.
+struct GbufSpecParams { uint32_t max_events; float reflect_threshold, roughness_max; };
+constexpr int GS_STACK = 8;
+__global__ void __launch_bounds__(GB_BLOCK) k_gbuffer_specular(DevScene sc, GbufParams gp, GbufSpecParams sp, rt_gbuffer_texel* out,
+                                                               rt_specular_texel2* chain_out, uint2* spill) {
+    __shared__ uint2 lds_stack[STACK_LDS*GB_BLOCK];
+    __shared__ float2 lds_bary[GB_BLOCK];
+    __shared__ uint32_t lds_mat[GS_STACK*GB_BLOCK];
+    Stack st;
+    st.lds = lds_stack; st.spill = spill; st.bary = lds_bary; st.lane = threadIdx.x; st.block = GB_BLOCK;
+    st.gtid = blockIdx.x*GB_BLOCK + threadIdx.x; st.nthreads = gridDim.x*GB_BLOCK;
+    uint32_t* mat = lds_mat + threadIdx.x;
+    const uint32_t n = gp.w*gp.h;
+    // camera (RT/raytracer.cpp:381-401), as gbuffer_pixels
+    const float hfw = gp.half_film_w*gp.focus_distance;
+    const float hfh = gp.half_film_h*gp.focus_distance;
+    const float film_distance = gp.focus_distance*gp.film_distance;
+    const V3 film_center = sub(gp.cp, smul(film_distance, gp.cz));
+    const float pixel_w = 1.0f / (float)gp.w, pixel_h = 1.0f / (float)gp.h;
+    for (uint64_t i = st.gtid; i < n; i += st.nthreads) {             // 64 bits: i + nthreads may pass 2^32
+        const uint32_t y = (uint32_t)i / gp.w, x = (uint32_t)i - y*gp.w;
+        float v = 1.0f - 2.0f*(float)y*pixel_h;
+        float u = 1.0f - 2.0f*(float)x*pixel_w;
+        apply_lens_distortion(gp.lens_distortion, gp.w, gp.h, u, v);
+        V3 film_p = film_center;
+        film_p = add(film_p, smul(u*hfw, gp.cx));
+        film_p = add(film_p, smul(v*hfh, gp.cy));
+        const V3 D = normalize(sub(film_p, gp.cp));
+        V3 ro = gp.cp, rd = D;
+        float T = 0.0f;
+        V3 m0 = {1.0f, 0.0f, 0.0f}, m1 = {0.0f, 1.0f, 0.0f}, m2 = {0.0f, 0.0f, 1.0f};      // M's rows
+        int32_t at = 0;
+        uint32_t events = 0, bits = 0, end = RT_SPECULAR_END_MISS;
+        uint32_t first_code = RT_HIT_MISS;
+        float first_t = 0.0f;
+        rt_gbuffer_texel g;
+        for (;;) {
+            Traversal<false> tr;
+            tr.init(sc, st, ro, rd, FLT_MAX_, 0u);
+            while (tr.mode != TM_DONE && tr.step(sc, st)) {}
+            const Hit h = tr.result(st);
+            if (h.code == RT_HIT_MISS) {
+                g.p = {D.x, D.y, D.z}; g.t = 0.0f; g.n = {0.0f, 0.0f, 0.0f}; g.primitive = RT_HIT_MISS;
+                break;                                                          // end stays RT_SPECULAR_END_MISS
+            }
+            Ray ray; ray.o = ro; ray.d = rd;
+            V3 I, N; uint32_t surf_id;
+            hit_geometry(sc, ray, h, I, N, surf_id);
+            g.primitive = h.code;
+            if (events == 0u) {
+                first_code = h.code; first_t = h.t;
+                T = h.t;
+                g.p = {I.x, I.y, I.z}; g.t = h.t; g.n = {N.x, N.y, N.z};
+            } else {
+                T = (T + EPSILON) + h.t;                                        // the ray started EPSILON along its direction
+                const V3 P = add(gp.cp, smul(T, D));
+                g.p = {P.x, P.y, P.z}; g.t = T; g.n = {dot(m0, N), dot(m1, N), dot(m2, N)};
+            }
+            // the vertex: shade_bounce_feat's steps 3-5
+            float cos_i = -dot(rd, N);
+            const bool inside = (cos_i < 0.0f);
+            uint32_t mi_id, mt_id;
+            if (inside) {
+                mi_id = surf_id;
+                const int32_t lv = at - 1 > 0 ? at - 1 : 0;
+                mt_id = lv ? mat[lv*GB_BLOCK] : sc.air_id;                      // level 0 = air
+                cos_i = -cos_i;
+                N = neg(N);
+            } else {
+                mi_id = at ? mat[at*GB_BLOCK] : sc.air_id;
+                mt_id = surf_id;
+            }
+            const rt_material mi = sc.materials[mi_id];
+            const rt_material mt = sc.materials[mt_id];
+            if (mt.flags & RT_MATERIAL_EMISSIVE) { end = RT_SPECULAR_END_EMITTER; break; }
+            const float eta_i = mi.ior, eta_t = mt.ior;
+            const float eta = eta_i / eta_t;
+            float cos_t;
+            float refl = fresnel_dielectric(cos_i, eta_i, eta_t, eta, cos_t);
+            refl = lerpf_(refl, 1.0f, mt.metallic);
+            V3 nd;
+            if (refl >= sp.reflect_threshold) {                                 // the majority lobe reflects
+                if (mt.roughness > sp.roughness_max) { end = RT_SPECULAR_END_ROUGH; break; }
+                if (events == sp.max_events) { end = RT_SPECULAR_END_CAP; break; }
+                nd = reflect(rd, N);
+                // M = M*(I - 2 N N^T).  Off the diagonal H is the negated product, not 0 - product: the two differ in
+                // the sign of a zero, which reaches n through M, and the negation is what the definition says
+                const V3 a = smul(2.0f, N);
+                const V3 h0 = {1.0f - a.x*N.x, -(a.x*N.y), -(a.x*N.z)};
+                const V3 h1 = {-(a.y*N.x), 1.0f - a.y*N.y, -(a.y*N.z)};
+                const V3 h2 = {-(a.z*N.x), -(a.z*N.y), 1.0f - a.z*N.z};
+                const V3 c0 = {h0.x, h1.x, h2.x}, c1 = {h0.y, h1.y, h2.y}, c2 = {h0.z, h1.z, h2.z};
+                m0 = {dot(m0, c0), dot(m0, c1), dot(m0, c2)};
+                m1 = {dot(m1, c0), dot(m1, c1), dot(m1, c2)};
+                m2 = {dot(m2, c0), dot(m2, c1), dot(m2, c2)};
+                bits |= 1u << (8u + events);
+            } else if (mt.is_participating_medium) {                            // refract
+                if (!inside && at >= GS_STACK - 1) { end = RT_SPECULAR_END_STACK; break; }
+                if (events == sp.max_events) { end = RT_SPECULAR_END_CAP; break; }
+                if (inside) {
+                    if (at > 0) --at;
+                } else {
+                    ++at;
+                    mat[at*GB_BLOCK] = mt_id;
+                }
+                nd = refract(rd, N, cos_i, cos_t, eta);
+            } else {                                                            // the diffuse branch
+                end = RT_SPECULAR_END_DIFFUSE;
+                break;
+            }
+            ro = add(I, smul(EPSILON, nd)); rd = nd;
+            ++events;
+        }
+        out[i] = g;
+        if (chain_out)
+            reinterpret_cast<uint4*>(chain_out)[i] = make_uint4(first_code, __float_as_uint(first_t), events | bits, end);
+    }
 }
 
 // k_post — the output pass (RT/raytracer.cpp:2103-2171): resolve, exposure,
@@ -6625,31 +6751,34 @@ int rt_debug_intersect(rt_scene* s, uint32_t count, const rt_ray_query* rays, in
 }
 
 namespace {
-int check_gbuffer(const char* entry, const rt_scene* s, const rt_camera* camera, uint32_t w, uint32_t h, const void* out,
-                  const char* out_name) {
+// what every G-buffer entry refuses before it looks at the scene
+int check_gbuffer_args(const char* entry, const rt_camera* camera, uint32_t w, uint32_t h, const void* out, const char* out_name) {
     const std::string e = entry;
     if (!camera) { set_error(e + ": null camera"); return RT_ERROR_INVALID; }
     if (!out) { set_error(e + ": null " + out_name); return RT_ERROR_INVALID; }
     if (!w) { set_error(e + ": w is 0"); return RT_ERROR_INVALID; }
     if (!h) { set_error(e + ": h is 0"); return RT_ERROR_INVALID; }
     if ((uint64_t)w*h > 0xFFFFFFFFull) { set_error(e + ": w*h must be below 2^32"); return RT_ERROR_INVALID; }
-    if (!s) { set_error(e + ": null scene"); return RT_ERROR_INVALID; }
+    return RT_OK;
+}
+int check_gbuffer(const char* entry, const rt_scene* s, const rt_camera* camera, uint32_t w, uint32_t h, const void* out,
+                  const char* out_name) {
+    int err = check_gbuffer_args(entry, camera, w, h, out, out_name);
+    if (err) return err;
+    if (!s) { set_error(std::string(entry) + ": null scene"); return RT_ERROR_INVALID; }
     return RT_OK;
 }
 }  // namespace
 
 namespace {
-// rt_gbuffer_device and rt_gbuffer_surface_device past their argument checks: d_surface null is the former
-int launch_gbuffer(const char* entry, rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t w, uint32_t h,
-                   rt_gbuffer_texel* d_out, rt_surface_texel* d_surface, void* hip_stream) {
-    int err = scene_stale(s, entry);
+// What the three G-buffer kernels' launches share: the device, the scene's spill area of the largest grid (once per
+// scene; rt_scene_free frees it), the camera as the kernels read it and the fixed grid.
+int prepare_gbuffer(rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t w, uint32_t h, GbufParams& gp,
+                    uint32_t& grid) {
+    int err = bind_device(s->device);
     if (err) return err;
-    err = bind_device(s->device);
-    if (err) return err;
-    // the spill area of the largest grid, once per scene (rt_scene_free frees it)
     if (!s->gbuf_spill)
         HIP_OK(hipMalloc(&s->gbuf_spill, sizeof(uint2)*(size_t)(STACK_DEPTH - STACK_LDS)*GB_MAX_GRID*GB_BLOCK));
-    GbufParams gp;
     gp.cp = rv3(c->p); gp.cx = rv3(c->x); gp.cy = rv3(c->y); gp.cz = rv3(c->z);
     gp.focus_distance = c->focus_distance;
     gp.film_distance = c->film_distance;
@@ -6658,7 +6787,19 @@ int launch_gbuffer(const char* entry, rt_scene* s, const rt_camera* c, float len
     gp.lens_distortion = lens_distortion;
     gp.w = w; gp.h = h;
     const uint64_t blocks = ((uint64_t)w*h + GB_BLOCK - 1) / GB_BLOCK;
-    const uint32_t grid = blocks < GB_MAX_GRID ? (uint32_t)blocks : GB_MAX_GRID;
+    grid = blocks < GB_MAX_GRID ? (uint32_t)blocks : GB_MAX_GRID;
+    return RT_OK;
+}
+
+// rt_gbuffer_device and rt_gbuffer_surface_device past their argument checks: d_surface null is the former
+int launch_gbuffer(const char* entry, rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t w, uint32_t h,
+                   rt_gbuffer_texel* d_out, rt_surface_texel* d_surface, void* hip_stream) {
+    int err = scene_stale(s, entry);
+    if (err) return err;
+    GbufParams gp;
+    uint32_t grid;
+    err = prepare_gbuffer(s, c, lens_distortion, w, h, gp, grid);
+    if (err) return err;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     if (d_surface) k_gbuffer_surface<<<grid, GB_BLOCK, 0, stream>>>(s->ds, gp, d_out, d_surface, s->gbuf_spill);
     else k_gbuffer<<<grid, GB_BLOCK, 0, stream>>>(s->ds, gp, d_out, s->gbuf_spill);
@@ -6722,6 +6863,69 @@ int rt_gbuffer(rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t 
     return err;
 }
 
+int rt_gbuffer_specular_default_params(rt_gbuffer_specular_params* out) {
+    if (!out) { set_error("rt_gbuffer_specular_default_params: null out"); return RT_ERROR_INVALID; }
+    out->max_events = 8u;
+    out->reflect_threshold = 0.5f;
+    out->roughness_max = 0.25f;
+    out->reserved = 0u;
+    return RT_OK;
+}
+
+namespace {
+int check_gbuffer_specular(const char* entry, const rt_scene* s, const rt_camera* camera, uint32_t w, uint32_t h,
+                           const rt_gbuffer_specular_params* p, const void* out, const char* out_name) {
+    // the parameters' refusals before the scene's: what needs no scene is refused without one
+    int err = check_gbuffer_args(entry, camera, w, h, out, out_name);
+    if (err) return err;
+    err = rt_internal_check_specular_params(entry, p);
+    if (err) return err;
+    if (!s) { set_error(std::string(entry) + ": null scene"); return RT_ERROR_INVALID; }
+    return scene_stale(s, entry);
+}
+}  // namespace
+
+int rt_gbuffer_specular_device(rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t w, uint32_t h,
+                               const rt_gbuffer_specular_params* p, rt_gbuffer_texel* d_out, rt_specular_texel2* d_chain,
+                               void* hip_stream) {
+    int err = check_gbuffer_specular("rt_gbuffer_specular_device", s, c, w, h, p, d_out, "d_out");
+    if (err) return err;
+    GbufParams gp;
+    uint32_t grid;
+    err = prepare_gbuffer(s, c, lens_distortion, w, h, gp, grid);
+    if (err) return err;
+    const GbufSpecParams sp = {p->max_events, p->reflect_threshold, p->roughness_max};
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    k_gbuffer_specular<<<grid, GB_BLOCK, 0, stream>>>(s->ds, gp, sp, d_out, d_chain, s->gbuf_spill);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
+int rt_gbuffer_specular(rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t w, uint32_t h,
+                        const rt_gbuffer_specular_params* p, rt_gbuffer_texel* out, rt_specular_texel2* chain) {
+    int err = check_gbuffer_specular("rt_gbuffer_specular", s, c, w, h, p, out, "out");
+    if (err) return err;
+    err = bind_device(s->device);
+    if (err) return err;
+    const size_t n = (size_t)w*h;
+    char* d = nullptr;
+    if (hipMalloc(&d, (sizeof(rt_gbuffer_texel) + sizeof(rt_specular_texel2))*n) != hipSuccess) {
+        set_error("rt_gbuffer_specular: hipMalloc");
+        return RT_ERROR_OUT_OF_MEMORY;
+    }
+    rt_gbuffer_texel* d_o = reinterpret_cast<rt_gbuffer_texel*>(d);
+    rt_specular_texel2* d_c = reinterpret_cast<rt_specular_texel2*>(d + sizeof(rt_gbuffer_texel)*n);
+    err = rt_gbuffer_specular_device(s, c, lens_distortion, w, h, p, d_o, chain ? d_c : nullptr, nullptr);
+    if (!err && (hipMemcpy(out, d_o, sizeof(rt_gbuffer_texel)*n, hipMemcpyDeviceToHost) != hipSuccess ||
+                 (chain && hipMemcpy(chain, d_c, sizeof(rt_specular_texel2)*n, hipMemcpyDeviceToHost) != hipSuccess))) {
+        set_error("rt_gbuffer_specular: copy out");
+        err = RT_ERROR_DEVICE;
+    }
+    (void)hipFree(d);
+    return err;
+}
+
 }  // extern "C"
 
 // Host helpers for the library's other translation units (rt_internal.h): rt_last_error's message, the
@@ -6729,6 +6933,21 @@ int rt_gbuffer(rt_scene* s, const rt_camera* c, float lens_distortion, uint32_t 
 #include "rt_internal.h"
 void rt_internal_set_error(const char* message) { set_error(message); }
 int rt_internal_bind_device(int device) { return bind_device(device); }
+int rt_internal_check_specular_params(const char* entry, const rt_gbuffer_specular_params* p) {
+    const std::string e = entry;
+    const auto bad = [](float v) { return !(v >= 0.0f) || v > FLT_MAX_; };      // negative, NaN or infinite
+    if (!p) { set_error(e + ": null rt_gbuffer_specular_params"); return RT_ERROR_INVALID; }
+    if (p->max_events > 16u) { set_error(e + ": rt_gbuffer_specular_params: max_events must be in 0..16"); return RT_ERROR_INVALID; }
+    if (bad(p->reflect_threshold)) {
+        set_error(e + ": rt_gbuffer_specular_params: reflect_threshold must be finite and >= 0");
+        return RT_ERROR_INVALID;
+    }
+    if (bad(p->roughness_max)) {
+        set_error(e + ": rt_gbuffer_specular_params: roughness_max must be finite and >= 0");
+        return RT_ERROR_INVALID;
+    }
+    return RT_OK;
+}
 int rt_internal_scene_device(const rt_scene* scene) { return scene->device; }
 int rt_internal_scene_cancelled(const rt_scene* scene) { return scene->cancel; }
 

@@ -431,6 +431,15 @@ int check_clip(const std::string& e, const char* prefix, const TaArgs& a) {
     return RT_OK;
 }
 
+// the drivers that clip (rt_clip.hip's and rt_specular.hip's): their rt_temporal_clip_params
+int check_clip_params(const std::string& e, const rt_temporal_clip_params* cp) {
+    if (!cp) return fail(RT_ERROR_INVALID, e + ": null rt_temporal_clip_params");
+    if (cp->radius < 1u || cp->radius > 3u) return fail(RT_ERROR_INVALID, e + ": rt_temporal_clip_params: radius must be in 1..3");
+    if (bad_value(cp->gamma)) return fail(RT_ERROR_INVALID, e + ": rt_temporal_clip_params: gamma must be finite and >= 0");
+    if (bad_value(cp->min_count)) return fail(RT_ERROR_INVALID, e + ": rt_temporal_clip_params: min_count must be finite and >= 0");
+    return RT_OK;
+}
+
 // the kernels' view of the previous camera; without a history nothing reads it
 TaCamera ta_camera(const TaArgs& a) {
     TaCamera cam = {};

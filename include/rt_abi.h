@@ -1280,6 +1280,71 @@ int rt_render_temporal_clipped(rt_scene* scene, const rt_camera* camera, const r
                                const rt_temporal_clip_params* cp, float* out_pixels, float* out_length,
                                float* out_clip_amount, rt_stats* stats);
 
+/* A specular G-buffer: a G-buffer that follows the camera ray through mirrors and glass (beyond the reference, an
+ * opt-in: new entries only, no other entry's behaviour changes; RT_ABI_VERSION stays).  DESIGN.md ("A specular
+ * G-buffer") defines the walk operation by operation; the kernel matches tests/ref_specular/ref_specular.c bit for bit.
+ *
+ * The camera ray is rt_gbuffer_device's.  At every hit the walk takes the majority lobe of the feature frames' vertex
+ * without a draw: it reflects perfectly where the Fresnel term (1 for total internal reflection, raised by
+ * `metallic`) is at least reflect_threshold, else refracts into a participating medium, else ends.  It carries the
+ * path length T, the product M of the reflections' Householder matrices and a material stack of 8 levels.  The texel of
+ * a walk that took no event is rt_gbuffer_device's bit for bit.  After events and a final hit it is the unfolded
+ * point: p = camera.p + T*D (D the camera ray's direction), t = T, n = M*N of the final hit, primitive the final
+ * hit's; after events and a miss it is {D, 0, 0, RT_HIT_MISS}.  For planar mirrors p is the mirror image of the
+ * surface seen, fixed in world space, so the temporal stages reproject it as they stand; through refraction it is an
+ * approximation their plane tolerance judges.
+ *
+ * The side record (d_chain, optional): the camera ray's own hit (first_primitive, first_t; RT_HIT_MISS and 0 on a
+ * miss), chain = the events taken in bits 0..7 and bit 8 + k set when event k was a reflection, end = why the walk
+ * ended.  No stage reads it.
+ *
+ * RT_ERROR_INVALID by name before any launch: rt_gbuffer_device's refusals, a NULL params, max_events above 16, a
+ * negative or non-finite reflect_threshold or roughness_max, a scene that awaits rt_scene_update_instances after
+ * rt_scene_update_mesh changed a mesh's bounds. */
+enum rt_specular_end {
+    RT_SPECULAR_END_MISS    = 0,   /* the last ray left the scene */
+    RT_SPECULAR_END_EMITTER = 1,   /* the material on the far side of the hit is emissive */
+    RT_SPECULAR_END_DIFFUSE = 2,   /* neither lobe was specular: the diffuse branch */
+    RT_SPECULAR_END_ROUGH   = 3,   /* a reflection off a material rougher than roughness_max */
+    RT_SPECULAR_END_STACK   = 4,   /* a refraction into a medium with the stack's 8 levels in use */
+    RT_SPECULAR_END_CAP     = 5    /* another event would pass max_events */
+};
+typedef struct rt_specular_texel2 { uint32_t first_primitive; float first_t; uint32_t chain, end; } rt_specular_texel2;  /* 16 B */
+typedef struct rt_gbuffer_specular_params {
+    uint32_t max_events;           /* 0..16; 0 is rt_gbuffer_device */
+    float    reflect_threshold;    /* a vertex reflects when its reflectance is at least this */
+    float    roughness_max;        /* a reflecting material rougher than this ends the walk as a surface */
+    uint32_t reserved;
+} rt_gbuffer_specular_params;
+int rt_gbuffer_specular_default_params(rt_gbuffer_specular_params* out);   /* 8, 0.5, 0.25; no device needed */
+int rt_gbuffer_specular_device(rt_scene* scene, const rt_camera* camera, float lens_distortion, uint32_t w, uint32_t h,
+                               const rt_gbuffer_specular_params* params, rt_gbuffer_texel* d_out,
+                               rt_specular_texel2* d_chain, void* hip_stream);
+/* Same, into host memory (chain may be NULL). */
+int rt_gbuffer_specular(rt_scene* scene, const rt_camera* camera, float lens_distortion, uint32_t w, uint32_t h,
+                        const rt_gbuffer_specular_params* params, rt_gbuffer_texel* out, rt_specular_texel2* chain);
+
+/* The driver: one frame of rt_render_temporal_device's loop over an rt_temporal_state with the specular G-buffer in
+ * rt_gbuffer_device's place.  cp NULL: the accumulate stage is rt_temporal_accumulate_device.  Otherwise the frame also
+ * runs rt_temporal_neighbourhood_device (cp->radius, p->firefly_clamp) and accumulates with
+ * rt_temporal_accumulate_clip_device (cp->gamma, cp->min_count) without motion, deform or surface tables.  The
+ * workspace is rt_temporal_workspace_bytes, then the neighbourhood texels on a 16-byte boundary (32 B a pixel).  A
+ * virtual point follows no motion or deform table: moved instances and deformed meshes are for the other drivers.
+ * rt_cancel, the restart rules and the refusals are rt_render_temporal_device's, plus the G-buffer's and, with a cp,
+ * the clipped driver's for it. */
+size_t rt_temporal_specular_workspace_bytes(uint32_t w, uint32_t h);   /* no device needed */
+int rt_render_temporal_specular_device(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                                       const rt_filter_cache* filter, const rt_tile_set* tiles,
+                                       uint32_t total_frame_index, uint32_t w, uint32_t h, uint32_t frame_count,
+                                       const rt_temporal_params* p, rt_temporal_state* state,
+                                       const rt_gbuffer_specular_params* sp, const rt_temporal_clip_params* cp,
+                                       float* d_out, float* d_length_out, void* hip_stream, rt_stats* stats);
+int rt_render_temporal_specular(rt_scene* scene, const rt_camera* camera, const rt_settings* settings,
+                                const rt_filter_cache* filter, const rt_tile_set* tiles, uint32_t total_frame_index,
+                                uint32_t w, uint32_t h, uint32_t frame_count, const rt_temporal_params* p,
+                                rt_temporal_state* state, const rt_gbuffer_specular_params* sp,
+                                const rt_temporal_clip_params* cp, float* out_pixels, float* out_length, rt_stats* stats);
+
 /* The reference's top-down BVH builders on the device (RT/bvh.cpp:222-326 with
  * partition_midpoint :53-61, partition_sah_binned :138-213 or the full SAH sweep
  * partition_objects_sah / evaluate_sah :63-131, the partition of :26-51): one launch per
